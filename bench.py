@@ -1,7 +1,15 @@
 """bench.py — scan-to-submap registration throughput on MI355X (driver contract).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3|c5]
+                  [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run does what the headline figure needs and no more: ray-cast the scans,
+prefill, warm up, time the K steps, write the last step's outputs (--dump-outputs) and
+print the line.  --full adds every secondary measurement described below (the other
+mode and the sequential-extraction line, the profiled pass with its roofline blocks and
+counters, concurrent streams, host input, the sharded C5 lines, the C2 / C3 sub-lines,
+the CPU baseline and the ATE block); the --no-* switches take single ones out again.
 
 A step = Estimator::register_scan of one synthetic organized scan (form/form.cpp:40-114):
 feature extraction, voxel-map build of the window keyscans, the ICP loop (match + LM
@@ -15,9 +23,16 @@ on the same ranks: one 2M-point scan registered against a replicated 50M-voxel
 submap, its points sharded over the ranks, the normal equations all-reduced over
 RCCL each ICP iteration (strong scaling).
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant
-kernel, HIP-event timed), `cpu_baseline` (the C++ oracle on the host cores, bounded
-sample of the same stream) and `sharded_c5`.
+Prints ONE JSON line (rank 0) with the contract fields; with --full also `roofline`
+(dominant kernel, HIP-event timed), `cpu_baseline` (the C++ oracle on the host cores,
+bounded sample of the same stream) and `sharded_c5`.
+
+--dump-outputs DIR: after the timed steps, what the last timed register_scan handed its
+caller (Estimator.register_scan's features and current_lidar_estimate's pose) is written
+as DIR/pose.npy (3x4 float64), DIR/planar.npy (F x 6 float32: xyz + normal) and
+DIR/point.npy (F x 3 float32); --workload c5: DIR/pose.npy (and pose_wholemap.npy), the
+pose of the last timed registration.  The scans are seeded, so equal arguments give
+equal inputs in every run.
 """
 from __future__ import annotations
 
@@ -45,6 +60,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="c4", choices=["c2", "c3", "c4", "c5"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements beside the headline (other mode, sequential "
+                         "extraction, profiled pass / roofline, concurrent streams, host input, sharded C5, "
+                         "C2 / C3 sub-lines, CPU baseline, ATE); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (rank 0)")
     ap.add_argument("--c5-side", type=int, default=7071, help="C5 terrain grid side (7071^2 = 50M voxels)")
     ap.add_argument("--c5-queries", type=int, default=2097152, help="C5 query points (2M)")
     ap.add_argument("--prefill", type=int, default=90,
@@ -727,6 +748,16 @@ def roofline(a, name, d, workload):
     return roof
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: one <name>.npy per output array of the last timed step (float32 or
+    float64 as the caller receives them; a few hundred KB in all)."""
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr)
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def rehearsal_record(out, a, world):
     """--rehearse-ranks: what the N-rank path produced, marked so no driver takes it for
     a measurement (the ranks shared one GPU)."""
@@ -746,9 +777,12 @@ def main():
     if a.workload == "c5":
         torch.cuda.set_device(local)
         dists = ("local", "wholemap") if a.c5_dist == "both" else (a.c5_dist,)
-        res = run_c5(a, rank, world, local, a.steps, a.warmup, dists=dists)
+        res = run_c5(a, rank, world, local, a.steps, a.warmup, profile=a.full, dists=dists)
         if res is not None:
             out = res[dists[0]]
+            if a.dump_outputs:
+                dump_outputs(a.dump_outputs, {"pose" if dn == dists[0] else f"pose_{dn}":
+                                              np.array(res[dn]["pose"], np.float64).reshape(3, 4) for dn in dists})
             if len(dists) > 1:
                 out["wholemap"] = res["wholemap"]
             if res.get("map_build"):
@@ -768,11 +802,13 @@ def main():
     # independent stream per rank (replicas): different trajectory phase
     world_obj = synth.World()
     k0 = 1000 * rank
-    psteps = a.steps if a.profile_steps is None else a.profile_steps
+    full = a.full
+    psteps = (a.steps if a.profile_steps is None else a.profile_steps) if full else 0
     pre = a.prefill
     total = pre + a.warmup + a.steps + psteps
+    # at least one scan past the timed ones: the last timed register_scan extracts it
     scans = [synth.raycast(world_obj, synth.trajectory_pose(k0 + k), geo, synth.SEED + 7919 * (k0 + k + 1), dev)
-             for k in range(total)]
+             for k in range(max(total, pre + a.warmup + a.steps + 1))]
     torch.cuda.synchronize()
     single = a.mode == "single"
 
@@ -801,11 +837,11 @@ def main():
                 "ms_per_step_p50": round(float(np.median(np.diff(mk))) * 1e3, 3)}
 
     ablation = None
-    if not a.no_ablation:
+    if full and not a.no_ablation:
         ablation = {"mode": "single-pose (disable_smoothing)" if not single else "smoothing (default)",
                     **secondary(not single, pipe)}
     # the same mode with every scan extracted inside its own register_scan (no fmx_next_scan)
-    sequential = secondary(single, False) if pipe else None
+    sequential = secondary(single, False) if full and pipe else None
     ctx = new_ctx(single)
     for k in range(pre + a.warmup):
         register(ctx, scans, k, pipe)
@@ -822,37 +858,47 @@ def main():
     torch.cuda.synchronize()
     barrier(world)
     t_local = time.perf_counter() - t0
-    # roofline pass: same stream continued, per-kernel HIP events on the context stream;
-    # the per-scan counters (ICP / LM iterations, round trips, ...) are read here too, so
-    # the timed loop above runs register_scan alone
-    ctx.profile(True)
-    ctx.profile_reset()
-    for k in range(pre + a.warmup + a.steps, total):
-        register(ctx, scans, k, pipe)
-        stats.append(ctx.last_stats())
-    ctx.sync()
-    prof = ctx.profile_read()
-    work = ctx.match_work()
-    mwork = ctx.profile_match_work()
-    ctx.profile(False)
+    if a.dump_outputs and rank == 0:
+        # what the last timed register_scan returned to its caller (fmx.Estimator): the
+        # scan's features, and its pose (current_lidar_estimate)
+        feats = ctx.extract_download()
+        dump_outputs(a.dump_outputs, {"pose": ctx.current_pose(), "planar": feats["planar"],
+                                      "point": feats["point"]})
+    prof, mwork = {}, {}
+    if full:
+        # roofline pass: same stream continued, per-kernel HIP events on the context stream;
+        # the per-scan counters (ICP / LM iterations, round trips, ...) are read here too, so
+        # the timed loop above runs register_scan alone
+        ctx.profile(True)
+        ctx.profile_reset()
+        for k in range(pre + a.warmup + a.steps, total):
+            register(ctx, scans, k, pipe)
+            stats.append(ctx.last_stats())
+        ctx.sync()
+        prof = ctx.profile_read()
+        work = ctx.match_work()
+        mwork = ctx.profile_match_work()
+        ctx.profile(False)
     ctx.close()
     multi = {}
-    for S in ([int(x) for x in a.streams.split(",") if x.strip()] if world == 1 else []):  # a per-GPU figure
+    for S in ([int(x) for x in a.streams.split(",") if x.strip()] if full and world == 1 else []):  # a per-GPU figure
         multi[str(S)] = concurrent_streams(S, new_ctx, scans, pre + a.warmup, a.steps, pipe, single, prev_aff)
     host_in = None
-    if world == 1 and not a.no_host_input:
+    if full and world == 1 and not a.no_host_input:
         host_in = host_input_block(a, new_ctx, scans, single, pre + a.warmup, a.steps)
     t_max = max_over_ranks(t_local, world, local)
     scans_total = sum_over_ranks(float(a.steps), world, local)
     # the sharded C5 registration beside the replica line: every rank takes part
     c5 = None
-    if not a.no_c5:  # each C5 line ends with a short profiled pass (its roofline block)
+    if full and not a.no_c5:  # each C5 line ends with a short profiled pass (its roofline block)
         c5 = run_c5(a, rank, world, local, a.c5_steps, a.c5_warmup, profile=True)
     # BASELINE's other scan configs beside the headline (every rank takes part)
     subs = {}
-    host = [s_.cpu().numpy() for s_ in scans[: min(total, 60)]] if not a.no_cpu_baseline and world == 1 else None
+    host = ([s_.cpu().numpy() for s_ in scans[: min(total, 60)]]
+            if full and not a.no_cpu_baseline and world == 1 else None)
     del scans
-    for wl in [w_.strip() for w_ in a.sub_workloads.split(",") if w_.strip() and w_.strip() != a.workload]:
+    for wl in [w_.strip() for w_ in a.sub_workloads.split(",")
+               if full and w_.strip() and w_.strip() != a.workload]:
         subs[wl] = sub_stream_line(a, wl, rank, world, local, single, pipe)
     c5_build = None
     if rank == 0 and c5 is not None:
@@ -866,18 +912,6 @@ def main():
         return
     value = scans_total / t_max
     ms_per_step = t_max / a.steps * 1e3
-    # dominant kernel by device time in the timed region
-    name, d = max(prof.items(), key=lambda kv: kv[1]["ms"])
-    roof = roofline(a, name, d, a.workload)
-    # the runner-up kernel class too (C4: match and the window linearization are within a
-    # few % of each other per scan)
-    ranked = sorted(prof.items(), key=lambda kv: -kv[1]["ms"])
-    roof_next = roofline(a, ranked[1][0], ranked[1][1], a.workload) if len(ranked) > 1 and ranked[1][1]["ms"] > 0 else None
-    st_mean = {k: float(np.mean([s[k] for s in stats])) for k in stats[0]} if stats else {}
-    kern_ms = {k: round(v["ms"] / max(psteps, 1), 4) for k, v in prof.items()}
-    kern_sum = sum(kern_ms.values())
-    side = {"map_build"} | ({"extract_rows", "closest", "fit", "compact"} if pipe else set())
-    main_ms = sum(v for k, v in kern_ms.items() if k not in side)
     out = {
         "metric": METRIC,
         "value": round(value, 3),
@@ -904,23 +938,39 @@ def main():
         "mpts_per_s": round(value * n_pts / 1e6, 3),
         # this rank's median per-scan wall time (host noise shows in the mean, not here)
         "ms_per_step_p50": round(float(np.median(np.diff(marks))) * 1e3, 3),
-        "roofline": roof,
-        "roofline_next": roof_next,
-        "kernels_ms_per_step": kern_ms,
-        "profile_steps": psteps,
-        # the context (critical-path) stream's kernel time per scan (profile pass, HIP
-        # events; its kernels never overlap each other) over the timed wall time per
-        # scan; side-stream work (pipelined extraction, map build) is excluded.  The
-        # rocprofv3 trace's own figure: profiles/critical_path_c4.json (tools/critical_path.py)
-        "main_stream_busy_frac": round(min(main_ms / ms_per_step, 1.0), 4) if ms_per_step > 0 else None,
-        "all_streams_kernel_ms_per_step": round(kern_sum, 4),
-        "host_round_trips_per_scan": round(st_mean.get("host_waits", 0.0), 2),
-        "counters": st_mean,
-        # every profiled match launch, each charged its own counters, cold (a scan's first
-        # match on its map) and warm (the ICP iterations after it) apart; certified: the
-        # warm queries the certificate settled without a search (fmx_match_cert)
-        "match_work_per_query": match_work_split(mwork),
     }
+    if full:  # the profiled pass's figures
+        # dominant kernel by device time in the timed region
+        name, d = max(prof.items(), key=lambda kv: kv[1]["ms"])
+        roof = roofline(a, name, d, a.workload)
+        # the runner-up kernel class too (C4: match and the window linearization are within a
+        # few % of each other per scan)
+        ranked = sorted(prof.items(), key=lambda kv: -kv[1]["ms"])
+        roof_next = (roofline(a, ranked[1][0], ranked[1][1], a.workload)
+                     if len(ranked) > 1 and ranked[1][1]["ms"] > 0 else None)
+        st_mean = {k: float(np.mean([s[k] for s in stats])) for k in stats[0]} if stats else {}
+        kern_ms = {k: round(v["ms"] / max(psteps, 1), 4) for k, v in prof.items()}
+        kern_sum = sum(kern_ms.values())
+        side = {"map_build"} | ({"extract_rows", "closest", "fit", "compact"} if pipe else set())
+        main_ms = sum(v for k, v in kern_ms.items() if k not in side)
+        out.update({
+            "roofline": roof,
+            "roofline_next": roof_next,
+            "kernels_ms_per_step": kern_ms,
+            "profile_steps": psteps,
+            # the context (critical-path) stream's kernel time per scan (profile pass, HIP
+            # events; its kernels never overlap each other) over the timed wall time per
+            # scan; side-stream work (pipelined extraction, map build) is excluded.  The
+            # rocprofv3 trace's own figure: profiles/critical_path_c4.json (tools/critical_path.py)
+            "main_stream_busy_frac": round(min(main_ms / ms_per_step, 1.0), 4) if ms_per_step > 0 else None,
+            "all_streams_kernel_ms_per_step": round(kern_sum, 4),
+            "host_round_trips_per_scan": round(st_mean.get("host_waits", 0.0), 2),
+            "counters": st_mean,
+            # every profiled match launch, each charged its own counters, cold (a scan's first
+            # match on its map) and warm (the ICP iterations after it) apart; certified: the
+            # warm queries the certificate settled without a search (fmx_match_cert)
+            "match_work_per_query": match_work_split(mwork),
+        })
     if multi:
         # S independent streams on one GPU (per rank), each its own context, stream and
         # host thread: aggregate scans/s and the per-stream rate.  Not the headline (a
@@ -955,7 +1005,7 @@ def main():
         if c5_build:
             out["c5_map_build"] = c5_build
     cp = os.path.join(ROOT, "profiles", f"critical_path_{a.workload}.json")
-    if os.path.exists(cp):  # a committed rocprofv3-trace figure, not measured by this run
+    if full and os.path.exists(cp):  # a committed rocprofv3-trace figure, not measured by this run
         with open(cp) as f:
             out["critical_path_trace"] = json.load(f)
         out["critical_path_trace"]["source"] = os.path.relpath(cp, ROOT)

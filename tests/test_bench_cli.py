@@ -43,6 +43,56 @@ def test_two_ranks_on_one_gpu_box_fails():
 
 
 @pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_plain_run_is_lean_and_dumps_last_step(fmx_mod, tmp_path):
+    """A plain run (no --full) prints the contract line without any secondary block, times
+    exactly --steps scans, and --dump-outputs writes what the last timed register_scan
+    returned: the same stream registered here gives the same features bit for bit and the
+    same pose (1e-9: the bar of the other cross-process pose comparison in this file)."""
+    import json
+
+    import numpy as np
+    import torch
+
+    from form_amd import synth
+    pre, warm, steps = 4, 1, 3
+    r = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warm), "--prefill", str(pre),
+              "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == steps and rec["warmup"] == warm and rec["unit"] == "scans/s"
+    assert rec["config"]["timed_scans"] == [pre + warm, pre + warm + steps]
+    assert rec["value"] > 0 and rec["higher_is_better"] is True and rec["dtype"] and rec["metric"]
+    assert abs(1e3 / rec["value"] - rec["ms_per_step"]) < 1e-3  # the time of one timed step (3 decimals)
+    for k in ("roofline", "kernels_ms_per_step", "cpu_baseline", "ate", "ablation", "sequential_extraction",
+              "concurrent_streams", "host_input", "sharded_c5", "c2", "c3", "critical_path_trace"):
+        assert k not in rec, k
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("pose", "planar", "point")}
+    assert got["pose"].dtype == np.float64 and got["pose"].shape == (3, 4)
+    assert got["planar"].dtype == np.float32 and got["planar"].shape[1] == 6 and len(got["planar"]) > 0
+    assert got["point"].dtype == np.float32 and got["point"].shape[1] == 3
+    assert sum(v.nbytes for v in got.values()) < 64 << 20
+    geo = synth.GEOMETRIES["c4"]
+    world = synth.World()
+    n = pre + warm + steps
+    scans = [synth.raycast(world, synth.trajectory_pose(k), geo, synth.SEED + 7919 * (k + 1), "cuda:0")
+             for k in range(n + 1)]
+    torch.cuda.synchronize()
+    ctx = fmx_mod.Context(fmx_mod.EstimatorParams(
+        extraction=fmx_mod.KeypointExtractionParams(**synth.default_params(geo)), voxel_subdivision=0))
+    for k in range(n):
+        ctx.next_scan(scans[k + 1])
+        ctx.register_scan(scans[k])
+    feats = ctx.extract_download()
+    pose = ctx.current_pose()
+    ctx.close()
+    assert np.array_equal(got["planar"], feats["planar"]) and np.array_equal(got["point"], feats["point"])
+    assert np.abs(got["pose"] - pose).max() < 1e-9, np.abs(got["pose"] - pose).max()
+
+
+@pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_rehearsed_two_rank_orchestration(fmx_mod):
     """The --gpus N path end to end on the 1-GPU box (--rehearse-ranks, test only):
@@ -57,7 +107,7 @@ def test_rehearsed_two_rank_orchestration(fmx_mod):
 
     from form_amd import shard, synth
     side, nq, w = 1501, 200000, 0.8
-    r = _run(["--gpus", "2", "--rehearse-ranks", "--steps", "3", "--warmup", "1", "--prefill", "4",
+    r = _run(["--gpus", "2", "--rehearse-ranks", "--full", "--steps", "3", "--warmup", "1", "--prefill", "4",
               "--c5-side", str(side), "--c5-queries", str(nq), "--c5-steps", "2", "--c5-warmup", "0",
               "--no-cpu-baseline", "--streams", "", "--no-ablation", "--sub-workloads", "", "--no-host-input",
               "--no-pin"])

@@ -7,7 +7,7 @@ mkdir -p gpurun_out/r4ab
 export TMPDIR=/tmp
 timeout -k 10 500 python -u -m pytest -x -q --timeout 300 --timeout-method thread -p no:cacheprovider tests/test_gpu_parity.py tests/test_gpu_map.py tests/test_gpu_configs.py tests/test_gpu_pipeline.py > gpurun_out/r4ab/tests_$V.log 2>&1 || { tail -30 gpurun_out/r4ab/tests_$V.log; exit 1; }
 tail -1 gpurun_out/r4ab/tests_$V.log
-B="python bench.py --steps 40 --warmup 10 --no-cpu-baseline --streams= --no-ablation --no-c5 --sub-workloads c2 --no-host-input"
+B="python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --streams= --no-ablation --no-c5 --sub-workloads c2 --no-host-input"
 for rep in $(seq 1 $N); do
   for tag in $V default; do
     unset FMX_LIB

@@ -21,7 +21,7 @@ if [ "${PART:-scan}" = scan ]; then
     for ctr in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
       i=$((i+1))
       rm -rf $D/$w/p$i
-      timeout -s KILL 300 rocprofv3 --pmc $ctr --kernel-include-regex "$RX" -d $D/$w/p$i -o run --output-format csv -- python bench.py --workload $w $B > $D/$w.p$i.json 2> $D/$w.p$i.err || { tail -20 $D/$w.p$i.err; exit 1; }
+      timeout -s KILL 300 rocprofv3 --pmc $ctr --kernel-include-regex "$RX" -d $D/$w/p$i -o run --output-format csv -- python bench.py --full --workload $w $B > $D/$w.p$i.json 2> $D/$w.p$i.err || { tail -20 $D/$w.p$i.err; exit 1; }
     done
     python tools/pmc_traffic.py $w $D/traffic_$w.json $D/$w/p1 $D/$w/p2 $D/$w/p3 > /dev/null || exit 1
     find $D/$w -name "*counter_collection.csv" -delete
@@ -31,14 +31,14 @@ for k,v in d['kernels'].items(): print('$w', k, v.get('hbm_bytes_per_launch'), r
   done
   if [ "${PMC:-1}" = 1 ]; then
     rm -rf $D/sq_c4
-    timeout -s KILL 300 rocprofv3 --pmc $SQ --kernel-include-regex "k_match" -d $D/sq_c4 -o run --output-format csv -- python bench.py --workload c4 $B > $D/sq_c4.out 2> $D/sq_c4.err || { tail -20 $D/sq_c4.err; exit 1; }
+    timeout -s KILL 300 rocprofv3 --pmc $SQ --kernel-include-regex "k_match" -d $D/sq_c4 -o run --output-format csv -- python bench.py --full --workload c4 $B > $D/sq_c4.out 2> $D/sq_c4.err || { tail -20 $D/sq_c4.err; exit 1; }
     python tools/pmc_traffic.py c4 $D/sq_wavestate_c4.json $D/sq_c4 > /dev/null || exit 1
     find $D/sq_c4 -name "*counter_collection.csv" -delete
   fi
   for w in ${CPATH:-c4 c2}; do
     rm -rf $D/prof_$w
     # --steps 40 (+ a 40-scan profile pass after them: skip 40)
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $D/prof_$w -o run --output-format csv -- python bench.py --workload $w --steps 40 --warmup 10 --no-cpu-baseline --no-c5 --no-ablation --sub-workloads= --no-host-input --streams= > $D/bench_prof_$w.json 2> $D/prof_$w.err || { tail -20 $D/prof_$w.err; exit 1; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $D/prof_$w -o run --output-format csv -- python bench.py --full --workload $w --steps 40 --warmup 10 --no-cpu-baseline --no-c5 --no-ablation --sub-workloads= --no-host-input --streams= > $D/bench_prof_$w.json 2> $D/prof_$w.err || { tail -20 $D/prof_$w.err; exit 1; }
     T=$(find $D/prof_$w -name "*kernel_trace.csv" | head -1)
     python tools/critical_path.py $T 40 $D/critical_path_$w.json 40 > /dev/null || exit 1
     python tools/trace_gaps.py $T > $D/trace_gaps_$w.txt 2>&1 || true

@@ -6,7 +6,7 @@ D=gpurun_out/end6
 mkdir -p $D
 for r in $(seq 1 ${REPS:-1}); do
   T0=$(date +%s.%N)
-  timeout -k 10 900 python bench.py > $D/bench_d$r.json 2> $D/bench_d$r.err || { tail -20 $D/bench_d$r.err; exit 1; }
+  timeout -k 10 900 python bench.py --full > $D/bench_d$r.json 2> $D/bench_d$r.err || { tail -20 $D/bench_d$r.err; exit 1; }
   T1=$(date +%s.%N)
   python - $D/bench_d$r.json "$T0" "$T1" <<'PY'
 import json, sys

@@ -8,7 +8,7 @@ D=gpurun_out/end6
 mkdir -p $D
 export TMPDIR=/tmp
 if [ "${PART:-bench}" = bench ]; then
-  timeout -k 10 900 python bench.py > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
+  timeout -k 10 900 python bench.py --full > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
   python - $D/bench.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -25,10 +25,10 @@ b = d.get("c5_map_build") or {}
 print("c5_map_build", b.get("ms_per_build"), json.dumps(b.get("roofline"))[:300])
 print("cpu_baseline", json.dumps(d.get("cpu_baseline"))[:300])
 PY
-  timeout -k 10 300 python bench.py --no-cpu-baseline --streams= --no-ablation --no-c5 --sub-workloads= > $D/host.json 2> $D/host.err || { tail -20 $D/host.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --streams= --no-ablation --no-c5 --sub-workloads= > $D/host.json 2> $D/host.err || { tail -20 $D/host.err; exit 1; }
   python -c "import json; d=json.loads(open('$D/host.json').read().strip().splitlines()[-1]); h=d['host_input']; print('host', d['value'], h['vs_device'], h['vs_device_p50'])"
 else
-  timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $D/prof -o run --output-format csv -- python bench.py > $D/bench_prof.json 2> $D/prof.err || { tail -20 $D/prof.err; exit 1; }
+  timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $D/prof -o run --output-format csv -- python bench.py --full > $D/bench_prof.json 2> $D/prof.err || { tail -20 $D/prof.err; exit 1; }
   find $D/prof -name "*kernel_trace.csv" -delete
   python tools/stats_fmx.py $(find $D/prof -name "*kernel_stats.csv" | head -1) > $D/kernel_stats_fmx.csv
   head -12 $D/kernel_stats_fmx.csv
