@@ -70,7 +70,7 @@ void match_counts_fetch(fmx_ctx* c, bool wait) {
 // ============================================================================ profiling
 static const char* kProfNames[PROF_COUNT] = {"extract_rows", "closest",   "fit",       "compact", "map_build",
                                              "match",        "pair_sort", "linearize", "insert",  "window",
-                                             "match_linearize", "unpack", "moments"};
+                                             "match_linearize", "unpack", "moments", "deskew"};
 
 ProfScope::ProfScope(Prof& p, int i, double by, hipStream_t s) : pr(p), id(i), bytes(by), st(s) {
   if (!pr.on) return;
@@ -475,8 +475,11 @@ const float4* stage_host_scan(fmx_ctx* c, const float* xyzw, size_t n) {
 }
 
 void pf_drop(fmx_ctx* c);
+// dsk_xi (register_scan with deskewing on): the scan is first moved to mid-sweep by this
+// twist, into the context's buffer on the context stream, and extracted from there; the
+// caller's scan is never written.
 void do_extract(fmx_ctx* c, const float* xyzw, size_t n, uint64_t scan, int on_dev, fmx_feature_counts* out,
-                const std::function<void()>& while_waiting = nullptr) {
+                const std::function<void()>& while_waiting = nullptr, const double* dsk_xi = nullptr) {
   const auto& E = c->P.extraction;
   const size_t R = (size_t)E.num_rows, C = (size_t)E.num_columns;
   if (!xyzw && n) throw StatusError(FMX_E_INVAL, "null scan");
@@ -487,6 +490,11 @@ void do_extract(fmx_ctx* c, const float* xyzw, size_t n, uint64_t scan, int on_d
     throw StatusError(FMX_E_INVAL, "unsupported scan geometry (columns must be <= 4096)");
   pf_drop(c);  // a queued extraction shares the scratch buffers
   const float4* d = on_dev ? reinterpret_cast<const float4*>(xyzw) : stage_host_scan(c, xyzw, n);
+  if (dsk_xi) {
+    c->dsk.out.ensure(n);  // sized by fmx_deskew_configure: no allocation here
+    run_deskew(c, d, c->dsk.out.p, c->dsk.have_frac ? c->dsk.frac.p : nullptr, (int)R, (int)C, dsk_xi, c->stream);
+    d = c->dsk.out.p;
+  }
   run_extract(c, d, (int)R, (int)C, out, while_waiting);
   c->q_scan = scan;
   c->have_queries = true;
@@ -505,7 +513,7 @@ void swap_query_set(fmx_ctx* c) {
 // Discard a queued extraction of an announced scan (its buffers are then free again).
 void pf_drop(fmx_ctx* c) {
   if (c->pf_launched) {
-    FMX_HIP(hipStreamSynchronize(c->side2));
+    FMX_HIP(hipStreamSynchronize(c->pf_L.st ? c->pf_L.st : c->side2));
     ++c->pf_dropped;
   }
   c->pf_launched = false;
@@ -520,8 +528,13 @@ void pf_drop(fmx_ctx* c) {
 // A host-announced scan is launched once its staging copy has finished (force: wait for
 // it): register_scan offers the launch after every ICP match and before the full LM,
 // and forces it at its end.
-void pf_launch(fmx_ctx* c, bool force = true) {
+// With deskewing on, the announced scan's twist depends on the final poses of the scan
+// being registered: its staging copy still starts early, but its DMA, deskew (dsk_xi,
+// into the context's second deskew buffer) and extraction are queued only by the call at
+// the end of register_scan, which passes the twist; the earlier offers are no-ops.
+void pf_launch(fmx_ctx* c, bool force = true, const double* dsk_xi = nullptr, int dsk_src = 0) {
   if (!c->ann_ptr || c->pf_launched) return;
+  if (c->dsk.on && !dsk_xi) return;
   if (c->ann_host && !c->ann_pinned) {
     StageReq& r = c->st_pf[c->ann_slot];
     if (!force && !r.complete()) return;
@@ -532,30 +545,44 @@ void pf_launch(fmx_ctx* c, bool force = true) {
   const float4* d = reinterpret_cast<const float4*>(c->ann_ptr);
   c->h_pf.ensure(8);
   if (c->pf_seq == 0) c->h_pf.p[4] = 0;
-  c->ev_pf_fork.record(c->stream);
-  FMX_HIP(hipStreamWaitEvent(c->side2, c->ev_pf_fork.last(), 0));
-  if (c->ann_host) {  // the staged copy -> the device (side2: behind the previous queued extraction's reads)
+  // deskewing: the context stream itself.  It has nothing left to do for this scan, the
+  // extraction is the first thing the next registration waits for, and the low-priority
+  // side stream's dispatch latency would then be on the critical path (measured: DESIGN.md)
+  const hipStream_t xs = c->dsk.on ? c->stream : c->side2;
+  if (xs != c->stream) {
+    c->ev_pf_fork.record(c->stream);
+    FMX_HIP(hipStreamWaitEvent(xs, c->ev_pf_fork.last(), 0));
+  }
+  if (c->ann_host) {  // the staged copy -> the device (xs: behind the previous queued extraction's reads)
     c->pf_scan.ensure(c->ann_n);
     if (c->ann_pinned) {
-      FMX_HIP(hipMemcpyAsync(c->pf_scan.p, c->ann_ptr, c->ann_n * sizeof(float4), hipMemcpyHostToDevice, c->side2));
+      FMX_HIP(hipMemcpyAsync(c->pf_scan.p, c->ann_ptr, c->ann_n * sizeof(float4), hipMemcpyHostToDevice, xs));
     } else {  // staged as packed x, y, z
       c->pf_scan3.ensure(3 * c->ann_n);
-      FMX_HIP(hipMemcpyAsync(c->pf_scan3.p, c->pin_pf[c->ann_slot], c->ann_n * 12, hipMemcpyHostToDevice, c->side2));
-      unpack_xyz(c, c->pf_scan3.p, c->pf_scan.p, c->ann_n, c->side2);
+      FMX_HIP(hipMemcpyAsync(c->pf_scan3.p, c->pin_pf[c->ann_slot], c->ann_n * 12, hipMemcpyHostToDevice, xs));
+      unpack_xyz(c, c->pf_scan3.p, c->pf_scan.p, c->ann_n, xs);
     }
     d = c->pf_scan.p;
+  }
+  if (c->dsk.on) {
+    c->dsk.pf_out.ensure(c->ann_n);  // sized by fmx_deskew_configure: no allocation here
+    run_deskew(c, d, c->dsk.pf_out.p, c->dsk.have_frac ? c->dsk.frac.p : nullptr, (int)E.num_rows, (int)E.num_columns,
+               dsk_xi, xs);
+    d = c->dsk.pf_out.p;
+    std::memcpy(c->dsk.pf_twist, dsk_xi, sizeof(c->dsk.pf_twist));
+    c->dsk.pf_src = dsk_src;
   }
   swap_query_set(c);
   try {
     const uint32_t seq = ++c->pf_seq;
-    c->pf_L = extract_launch(c, d, (int)E.num_rows, (int)E.num_columns, c->side2, c->h_pf.p, c->h_pf.d, c->h_pf.p + 4,
+    c->pf_L = extract_launch(c, d, (int)E.num_rows, (int)E.num_columns, xs, c->h_pf.p, c->h_pf.d, c->h_pf.p + 4,
                              c->h_pf.d + 4, seq);
   } catch (...) {
     swap_query_set(c);
     throw;
   }
   swap_query_set(c);
-  c->ev_pf.record(c->side2);
+  c->ev_pf.record(xs);
   c->pf_launched = true;
   c->pf_ptr = c->ann_ptr;
   c->pf_n = c->ann_n;
@@ -566,7 +593,10 @@ void pf_launch(fmx_ctx* c, bool force = true) {
 // register_scan(scan): true if `scan` is the one whose extraction was queued; its query
 // set becomes current (the context stream waits for its kernels) and its totals are
 // collected.  Any other scan drops the queued extraction.
-bool pf_take(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, uint64_t scan, fmx_feature_counts* out) {
+// while_waiting (deskewing: the extraction was queued only at the end of the previous
+// registration and may still be running): host work to do first if it has not finished.
+bool pf_take(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, uint64_t scan, fmx_feature_counts* out,
+             const std::function<void()>* while_waiting = nullptr) {
   if (!c->pf_launched) return false;
   if ((on_dev != 0) == c->pf_host || xyzw != c->pf_ptr || n != c->pf_n) {
     pf_drop(c);
@@ -576,6 +606,7 @@ bool pf_take(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, uint64_t scan,
   c->pf_ptr = nullptr;
   swap_query_set(c);
   FMX_HIP(hipStreamWaitEvent(c->stream, c->ev_pf.last(), 0));
+  if (while_waiting && !flag_reached(*c->pf_L.flag, c->pf_L.seq)) (*while_waiting)();
   extract_collect(c, c->pf_L, out);
   ++c->pf_used;
   c->q_scan = scan;
@@ -642,6 +673,29 @@ Pose predict_next(const fmx_ctx::Est& e, const std::vector<uint64_t>& gone = {})
   }
   if (pe) return e.values.at(s - 1);
   return identity();
+}
+
+// Deskewing: the twist of the scan after e.scan when the caller supplied none — the
+// constant-velocity twist Log(T_{j-2}^-1 T_{j-1}) of the two poses predict_next reads
+// (same handling of the keys a pending marginalization is about to erase), else the
+// configured initial twist.  Returns fmx_deskew_last's source (2 / 1).  The window poses
+// do not move between the end of one register_scan and the next one's prepare()
+// (marginalization moves no pose), so both places compute the same bits.
+int deskew_next_twist(const fmx_ctx* c, double xi[6]) {
+  const fmx_ctx::Est* e = c->est;
+  if (e && e->init) {
+    const uint64_t s = e->scan + 1;
+    auto has = [&](uint64_t k) {
+      return e->values.count(k) && !(e->tail_pending &&
+                                     std::find(e->tail_marg.begin(), e->tail_marg.end(), k) != e->tail_marg.end());
+    };
+    if (s > 1 && has(s - 1) && has(s - 2)) {
+      logmap(compose(inverse(e->values.at(s - 2)), e->values.at(s - 1)), xi);
+      return 2;
+    }
+  }
+  std::memcpy(xi, c->dsk.initial, 6 * sizeof(double));
+  return 1;
 }
 
 // Single-pose LM on X(j), map poses fixed (disable_smoothing, constraints.cpp:103-111,
@@ -1418,13 +1472,42 @@ void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feat
     }
     e.spec_map = false;
   };
+  // Deskewing: this scan's twist, from the window values as they stand now (prepare()
+  // runs inside the extraction's wait, after the deskew kernel was queued).  A one-shot
+  // caller twist wins; an extraction queued with another twist is dropped and redone here.
+  double dsk_xi[6] = {};
+  int dsk_src = 0;
+  if (c->dsk.on) {
+    if (c->dsk.one_shot) {
+      std::memcpy(dsk_xi, c->dsk.caller, sizeof(dsk_xi));
+      dsk_src = 3;
+      pf_drop(c);
+      c->dsk.one_shot = false;
+    } else {
+      dsk_src = deskew_next_twist(c, dsk_xi);
+    }
+  }
   {
     HostScope hs_ex(2);
-    if (pf_take(c, xyzw, n, on_dev, j, &fc)) {
+    // deskewing: a queued extraction started only when the previous registration ended;
+    // if it is still running, this scan's host work goes first, as on the sequential path
+    bool host_done = false;
+    std::function<void()> host_first;  // left empty with deskewing off: that path is untouched
+    if (c->dsk.on)
+      host_first = [&] {
+        map_inputs();
+        finish();
+        host_done = true;
+      };
+    if (pf_take(c, xyzw, n, on_dev, j, &fc, c->dsk.on ? &host_first : nullptr)) {
+      if (c->dsk.on) {  // the queued extraction's twist (computed from the same poses)
+        std::memcpy(dsk_xi, c->dsk.pf_twist, sizeof(dsk_xi));
+        dsk_src = c->dsk.pf_src;
+      }
       // pipelined: the features were extracted during the previous registration.  The
       // first ICP match (at the prediction) is queued before the host's finish() work,
       // which then overlaps it; the ICP loop takes it as a speculative match.
-      map_inputs();
+      if (!host_done) map_inputs();
       FMX_HIP(hipStreamWaitEvent(c->stream, c->ev_join.last(), 0));
       if (!P.disable_smoothing) {
         if (!lin_rows()) {  // + the first ICP iteration's moments (its x0: the window values)
@@ -1436,14 +1519,16 @@ void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feat
           spec_match(c, e.values.at(j).m, true);
         }
       }
-      finish();
+      if (!host_done) finish();
     } else {
       do_extract(c, xyzw, n, j, on_dev, &fc, [&] {
         map_inputs();
         finish();
-      });
+      }, c->dsk.on ? dsk_xi : nullptr);
     }
   }
+  std::memcpy(c->dsk.last, dsk_xi, sizeof(dsk_xi));
+  c->dsk.last_src = dsk_src;
   FMX_HIP(hipStreamWaitEvent(c->stream, c->ev_join.last(), 0));
   FMX_TRACE_("scan %llu: extracted %u + %u, map queued\n", (unsigned long long)j, fc.planar, fc.point);
   HostScope* hs_icp = new HostScope(4);
@@ -1498,6 +1583,14 @@ void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feat
     ensure_pool_room(c, 1, c->n_qpt);
     run_insert(c, j, nullptr);
     keyscan_step(c, e, j, fc.planar + fc.point);  // marginalization: deferred (finish_tail)
+  }
+  if (c->dsk.on && c->ann_ptr && !c->pf_launched) {
+    // deskewing: the announced scan's twist needs this scan's final poses and the keyscan
+    // step's verdict, both in by now; its deskew + extraction overlap the rest of this
+    // call and the caller's time until the next one
+    double nxt[6];
+    const int src = deskew_next_twist(c, nxt);
+    pf_launch(c, true, nxt, src);
   }
   FMX_TRACE_("scan %llu: done\n", (unsigned long long)j);
   c->stats[0] = icp;
@@ -1650,6 +1743,11 @@ void fmx_destroy(fmx_ctx* c) {
   c->pf_scan.release();
   c->scan3.release();
   c->pf_scan3.release();
+  c->dsk.frac.release();
+  c->dsk.out.release();
+  c->dsk.pf_out.release();
+  c->dsk.io_in.release();
+  c->dsk.io_out.release();
   for (auto& B : c->scanbuf)
     if (B.p) (void)hipHostFree(B.p);
   for (int t = 0; t < 2; ++t) {
@@ -2036,7 +2134,8 @@ fmx_status fmx_next_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev) {
                            ? c->ann_slot ^ 1
                            : (c->pf_launched && c->pf_host && c->pf_slot >= 0 ? c->pf_slot ^ 1 : 0);
       // the slot's pinned bytes may still feed the DMA of a queued, not yet taken extraction
-      if (c->pf_launched && c->pf_host && c->pf_slot == slot) FMX_HIP(hipStreamSynchronize(c->side2));
+      if (c->pf_launched && c->pf_host && c->pf_slot == slot)
+        FMX_HIP(hipStreamSynchronize(c->pf_L.st ? c->pf_L.st : c->side2));
       stage_submit(c, c->st_pf[slot], xyzw, c->pin_pf[slot], n * sizeof(float4));
       if (c->stager.threads() == 0) stage_finish(c, c->st_pf[slot]);
       c->ann_slot = slot;
@@ -2044,6 +2143,90 @@ fmx_status fmx_next_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev) {
     c->ann_host = !on_dev;
     c->ann_ptr = xyzw;
     c->ann_n = n;
+  });
+}
+
+// ---- scan deskewing (deskew.hip)
+fmx_status fmx_deskew_configure(fmx_ctx* c, const fmx_deskew_params* p) {
+  return guard<false>(c, [&] {
+    if (!p) throw StatusError(FMX_E_INVAL, "null deskew parameters");
+    if (c->est) throw StatusError(FMX_E_STATE, "fmx_deskew_configure after the first fmx_register_scan");
+    const auto& E = c->P.extraction;
+    if (E.num_rows <= 0 || E.num_columns <= 0) throw StatusError(FMX_E_INVAL, "no scan geometry");
+    const size_t C = (size_t)E.num_columns, n = (size_t)E.num_rows * C;
+    for (int k = 0; k < 6; ++k)
+      if (!std::isfinite(p->initial_twist[k])) throw StatusError(FMX_E_INVAL, "non-finite initial twist");
+    if (p->column_fraction)
+      for (size_t k = 0; k < C; ++k)
+        if (!(p->column_fraction[k] >= 0.0f && p->column_fraction[k] <= 1.0f))  // also rejects NaN
+          throw StatusError(FMX_E_INVAL, "column fraction " + std::to_string(k) + " outside [0, 1]");
+    sync_all(c);  // an earlier fmx_deskew may still read the table
+    c->dsk.have_frac = p->column_fraction != nullptr;
+    if (c->dsk.have_frac) {
+      c->dsk.frac.ensure(C);
+      FMX_HIP(hipMemcpy(c->dsk.frac.p, p->column_fraction, C * sizeof(float), hipMemcpyHostToDevice));
+    }
+    c->dsk.on = p->enable != 0;
+    std::memcpy(c->dsk.initial, p->initial_twist, sizeof(c->dsk.initial));
+    c->dsk.one_shot = false;
+    if (c->dsk.on) {  // every per-scan buffer now: registration allocates nothing for it
+      c->dsk.out.ensure(n);
+      c->dsk.pf_out.ensure(n);
+    }
+  });
+}
+
+fmx_status fmx_deskew_set_twist(fmx_ctx* c, const double twist[6]) {
+  return guard<false>(c, [&] {
+    if (!twist) throw StatusError(FMX_E_INVAL, "null twist");
+    for (int k = 0; k < 6; ++k)
+      if (!std::isfinite(twist[k])) throw StatusError(FMX_E_INVAL, "non-finite twist");
+    if (!c->dsk.on) throw StatusError(FMX_E_STATE, "deskewing is not enabled (fmx_deskew_configure)");
+    std::memcpy(c->dsk.caller, twist, sizeof(c->dsk.caller));
+    c->dsk.one_shot = true;
+    // an announced scan already extracted with the constant-velocity twist: dropped,
+    // its own fmx_register_scan extracts it again with this one
+    if (c->pf_launched) pf_drop(c);
+  });
+}
+
+fmx_status fmx_deskew_last(fmx_ctx* c, double twist[6], int* source) {
+  return guard<false>(c, [&] {
+    if (twist) std::memcpy(twist, c->dsk.last, sizeof(c->dsk.last));
+    if (source) *source = c->dsk.last_src;
+  });
+}
+
+fmx_status fmx_deskew(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double twist[6], float* out,
+                      int dst_on_dev) {
+  return guard<false>(c, [&] {
+    const auto& E = c->P.extraction;
+    const size_t R = (size_t)(E.num_rows > 0 ? E.num_rows : 0), C = (size_t)(E.num_columns > 0 ? E.num_columns : 0);
+    if (!xyzw || !out || !twist) throw StatusError(FMX_E_INVAL, "null scan / output / twist");
+    if (n == 0 || n != R * C)
+      throw StatusError(FMX_E_SIZE, "Provided scan does not match the expected size " + std::to_string(R * C) +
+                                        " != " + std::to_string(n));
+    for (int k = 0; k < 6; ++k)
+      if (!std::isfinite(twist[k])) throw StatusError(FMX_E_INVAL, "non-finite twist");
+    if ((src_on_dev != 0) == (dst_on_dev != 0)) {  // same memory kind: the ranges must not overlap
+      const uintptr_t a = reinterpret_cast<uintptr_t>(xyzw), b = reinterpret_cast<uintptr_t>(out);
+      const uintptr_t bytes = n * sizeof(float4);
+      if (a < b + bytes && b < a + bytes) throw StatusError(FMX_E_INVAL, "fmx_deskew: out aliases in");
+    }
+    const float4* d_in = reinterpret_cast<const float4*>(xyzw);
+    float4* d_out = reinterpret_cast<float4*>(out);
+    if (!src_on_dev) {
+      c->dsk.io_in.ensure(n);
+      FMX_HIP(hipMemcpyAsync(c->dsk.io_in.p, xyzw, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+      d_in = c->dsk.io_in.p;
+    }
+    if (!dst_on_dev) {
+      c->dsk.io_out.ensure(n);
+      d_out = c->dsk.io_out.p;
+    }
+    run_deskew(c, d_in, d_out, c->dsk.have_frac ? c->dsk.frac.p : nullptr, (int)R, (int)C, twist, c->stream);
+    if (!dst_on_dev) FMX_HIP(hipMemcpyAsync(out, d_out, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns in / out again
   });
 }
 

@@ -132,6 +132,7 @@ enum ProfId {
   PROF_MATCH_LIN,
   PROF_UNPACK,
   PROF_MOMENTS,
+  PROF_DESKEW,
   PROF_COUNT
 };
 
@@ -394,6 +395,23 @@ struct fmx_ctx {
     size_t cap = 0;
   } scanbuf[3];
   int scanbuf_next = 0;
+
+  // ---- scan deskewing (deskew.hip; fmx_deskew_configure).  Off unless configured: no
+  // buffer below is then allocated and no entry point behaves differently.
+  struct Deskew {
+    bool on = false;
+    double initial[6] = {};        // twist of scans without both window predecessors
+    bool have_frac = false;
+    fmx::DBuf<float> frac;         // per-column sweep fractions (uploaded at configure time)
+    fmx::DBuf<float4> out, pf_out; // deskewed scan: sequential path / queued extraction
+    fmx::DBuf<float4> io_in, io_out;  // fmx_deskew with host memory
+    bool one_shot = false;         // fmx_deskew_set_twist since the last registration
+    double caller[6] = {};
+    double last[6] = {};           // what the last fmx_register_scan used
+    int last_src = 0;              // 0 none/off, 1 initial, 2 constant velocity, 3 caller
+    double pf_twist[6] = {};       // ... what the queued extraction used
+    int pf_src = 0;
+  } dsk;
 
   // ---- window keypoint store + maps
   fmx::Pool pool[2];
@@ -769,6 +787,10 @@ ExLaunch extract_launch(fmx_ctx* c, const float4* d_scan, int R, int C, hipStrea
 void extract_collect(fmx_ctx* c, const ExLaunch& L, fmx_feature_counts* out);
 void run_extract(fmx_ctx* c, const float4* d_scan, int R, int C, fmx_feature_counts* out,
                  const std::function<void()>& while_waiting = nullptr);
+// deskew.hip: d_in -> d_out (R * C float4 each, not aliased) moved to mid-sweep by the
+// twist xi; d_frac: C per-column sweep fractions, or null for c / C
+void run_deskew(fmx_ctx* c, const float4* d_in, float4* d_out, const float* d_frac, int R, int C,
+                const double xi[6], hipStream_t st);
 // packed x, y, z (a staged host scan) -> float4 points with pad 0, on stream st
 void unpack_xyz(fmx_ctx* c, const float* d_packed, float4* d_out, size_t n, hipStream_t st);
 // st: stream to build on (default the context stream; register_scan uses the side

@@ -56,6 +56,10 @@ class _Params(C.Structure):
     ]
 
 
+class _DeskewParams(C.Structure):
+    _fields_ = [("enable", C.c_int32), ("initial_twist", C.c_double * 6), ("column_fraction", C.c_void_p)]
+
+
 class _Counts(C.Structure):
     _fields_ = [("planar", C.c_uint32), ("point", C.c_uint32), ("planar_selected", C.c_uint32)]
 
@@ -84,6 +88,7 @@ EXPORTED = [
     "fmx_profile_name", "fmx_profile_read", "fmx_sync", "fmx_comm_unique_id", "fmx_comm_init",
     "fmx_map_download", "fmx_register_points", "fmx_scan_buffer", "fmx_match_cert", "fmx_profile_match_work",
     "fmx_corr_generation", "fmx_moments", "fmx_moments_contract",
+    "fmx_deskew_configure", "fmx_deskew_set_twist", "fmx_deskew_last", "fmx_deskew",
 ]
 
 
@@ -374,6 +379,63 @@ class Context:
         # the tensor must outlive the extraction queued for it
         self._pf_keep = (getattr(self, "_pf_keep", (None, None))[1], scan)
 
+    # ---------------------------------------------------------------- deskewing
+    def deskew_configure(self, enable: bool = True, initial_twist=None, column_fraction=None):
+        """fmx_deskew_configure (before the first register_scan): constant-velocity
+        deskewing of every registered scan to mid-sweep.  initial_twist: [w; v] per scan
+        period for the scans without two predecessors (default 0); column_fraction:
+        per-column sweep fractions in [0, 1] (default c / cols)."""
+        p = _DeskewParams()
+        p.enable = int(bool(enable))
+        xi = np.zeros(6) if initial_twist is None else np.ascontiguousarray(initial_twist, np.float64).reshape(6)
+        for k in range(6):
+            p.initial_twist[k] = float(xi[k])
+        frac = None
+        if column_fraction is not None:
+            frac = np.ascontiguousarray(column_fraction, np.float32).reshape(-1)
+            if len(frac) != self.params.extraction.num_columns:
+                raise ValueError("column_fraction needs one value per scan column")
+            p.column_fraction = frac.ctypes.data
+        self._chk(self._L.fmx_deskew_configure(self.h, C.byref(p)))
+        del frac
+
+    def deskew_set_twist(self, twist):
+        """fmx_deskew_set_twist: the twist ([w; v] per scan period, e.g. integrated IMU /
+        wheel odometry) the next register_scan deskews with, once."""
+        xi = np.ascontiguousarray(twist, np.float64).reshape(6)
+        self._chk(self._L.fmx_deskew_set_twist(self.h, _p(xi)))
+
+    def deskew_last(self):
+        """fmx_deskew_last: (twist (6,), source) of the last register_scan; source 0
+        none/off, 1 initial, 2 constant velocity, 3 caller."""
+        xi = np.zeros(6)
+        src = C.c_int(0)
+        self._chk(self._L.fmx_deskew_last(self.h, _p(xi), C.byref(src)))
+        return xi, int(src.value)
+
+    def deskew(self, scan, twist, out=None):
+        """fmx_deskew: one rows * cols scan moved to mid-sweep by `twist` with the
+        registration's kernel.  A CUDA tensor gives a new CUDA tensor (or fills `out`, a
+        CUDA tensor of the same shape); host input gives a numpy array."""
+        on_dev, ptr, n, keep = _scan_ptr(scan)
+        xi = np.ascontiguousarray(twist, np.float64).reshape(6)
+        if on_dev:
+            import torch
+            res = torch.empty_like(keep) if out is None else out
+            if not (res.is_cuda and res.is_contiguous() and res.dtype == keep.dtype and res.shape == keep.shape):
+                raise ValueError("out must be a contiguous (N, 4) float32 CUDA tensor")
+            _ready(keep, res)
+            optr = C.c_void_p(res.data_ptr())
+        else:
+            res = np.empty((n, 4), np.float32) if out is None else out
+            if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (n, 4)
+                    and res.flags.c_contiguous):
+                raise ValueError("out must be a contiguous (N, 4) float32 array")
+            optr = _p(res)
+        self._chk(self._L.fmx_deskew(self.h, ptr, C.c_size_t(n), C.c_int(on_dev), _p(xi), optr, C.c_int(on_dev)))
+        del keep
+        return res
+
     def current_pose(self) -> np.ndarray:
         T = np.zeros(12)
         self._chk(self._L.fmx_current_pose(self.h, _p(T)))
@@ -618,6 +680,7 @@ class FORM:
         self._est = None
         self._scan = -1
         self._pose = np.eye(4)
+        self._deskew = None  # set_deskew's arguments, applied by initialize()
 
     @staticmethod
     def name() -> str:
@@ -681,8 +744,19 @@ class FORM:
         if self._est is not None:
             self._est.close()
         self._est = Context(self.params, self.device)
+        if self._deskew is not None:
+            self._est.deskew_configure(*self._deskew)
         self._scan = -1
         self._pose = np.eye(4)
+
+    def set_deskew(self, enable: bool = True, initial_twist=None, column_fraction=None) -> None:
+        """Constant-velocity deskewing of every scan to mid-sweep (fmx_deskew_configure;
+        no reference counterpart, so not a pipeline YAML key).  Applied by initialize().
+        initial_twist: [w; v] per scan period for the first two scans (default: at rest);
+        column_fraction: per-column sweep fractions in [0, 1] (default c / cols)."""
+        self._deskew = (bool(enable),
+                        None if initial_twist is None else np.array(initial_twist, np.float64).reshape(6),
+                        None if column_fraction is None else np.array(column_fraction, np.float32).reshape(-1))
 
     def add_imu(self, mm) -> None:  # bindings.cpp:144 (unused)
         pass
@@ -714,7 +788,9 @@ class FORM:
         return {"planar": planar, "point": point}
 
     def pose(self) -> np.ndarray:
-        """bindings.cpp:93: the latest pose (4 x 4)."""
+        """bindings.cpp:93: the latest pose (4 x 4).  With deskewing on (set_deskew) it is
+        the pose at the middle of the last sweep, and add_lidar's features are in that
+        frame."""
         return self._pose.copy()
 
     def map(self) -> dict:

@@ -174,6 +174,96 @@ def make_scan(config: str = "tiny", k: int = 0, seed: int = SEED, device="cpu", 
     return raycast(w, T, geo, seed + 7919 * (k + 1), device), T, geo
 
 
+def raycast_skewed(world: World, pose_fn, geo: ScanGeometry, seed: int, fractions=None, device="cpu") -> torch.Tensor:
+    """A motion-distorted sweep: column c is cast from the sensor pose pose_fn(s_c) (3x4)
+    at its sweep fraction s_c = fractions[c] (default c / cols), each point in the frame
+    of its own column's pose.  Same scene tests, noise and dropout stream as raycast, with
+    a per-ray origin and rotation in the same operation order: with one constant pose the
+    output equals raycast's bit for bit."""
+    dev = torch.device(device)
+    d_s = _ray_dirs(geo, dev)
+    n = d_s.shape[0]
+    if fractions is None:
+        fractions = np.arange(geo.cols) / geo.cols
+    P = np.stack([np.asarray(pose_fn(float(s)), np.float64).reshape(3, 4) for s in fractions])  # (cols, 3, 4)
+    Pc = torch.as_tensor(P, device=dev, dtype=torch.float64)
+    col = torch.arange(n, device=dev) % geo.cols
+    o = Pc[:, :, 3][col]  # (n, 3) ray origins
+    # world directions, one column at a time: d_s @ R.T as raycast computes it
+    d = torch.empty_like(d_s)
+    d3 = d.view(geo.rows, geo.cols, 3)
+    s3 = d_s.view(geo.rows, geo.cols, 3)
+    for c in range(geo.cols):
+        d3[:, c, :] = s3[:, c, :] @ Pc[c, :, :3].T
+    best = torch.full((n,), float("inf"), device=dev, dtype=torch.float64)
+    inv = 1.0 / torch.where(d.abs() < 1e-12, torch.full_like(d, 1e-12), d)
+
+    room = torch.as_tensor(world.room, device=dev, dtype=torch.float64)
+    t_lo = (room[:, 0] - o) * inv
+    t_hi = (room[:, 1] - o) * inv
+    t_exit = torch.maximum(t_lo, t_hi).min(dim=1).values
+    best = torch.minimum(best, t_exit)
+
+    bc = torch.as_tensor(world.box_c, device=dev, dtype=torch.float64)
+    bh = torch.as_tensor(world.box_h, device=dev, dtype=torch.float64)
+    yaw = torch.as_tensor(world.box_yaw, device=dev, dtype=torch.float64)
+    c, s = torch.cos(yaw), torch.sin(yaw)
+    for b in range(bc.shape[0]):
+        ob = o - bc[b]
+        obx = c[b] * ob[:, 0] + s[b] * ob[:, 1]
+        oby = -s[b] * ob[:, 0] + c[b] * ob[:, 1]
+        dbx = c[b] * d[:, 0] + s[b] * d[:, 1]
+        dby = -s[b] * d[:, 0] + c[b] * d[:, 1]
+        dbz = d[:, 2]
+        tmin = torch.full((n,), -float("inf"), device=dev, dtype=torch.float64)
+        tmax = torch.full((n,), float("inf"), device=dev, dtype=torch.float64)
+        for oo, dd, h in ((obx, dbx, bh[b, 0]), (oby, dby, bh[b, 1]), (ob[:, 2], dbz, bh[b, 2])):
+            dd = torch.where(dd.abs() < 1e-12, torch.full_like(dd, 1e-12), dd)
+            t1 = (-h - oo) / dd
+            t2 = (h - oo) / dd
+            tmin = torch.maximum(tmin, torch.minimum(t1, t2))
+            tmax = torch.minimum(tmax, torch.maximum(t1, t2))
+        hit = (tmax >= tmin) & (tmin > 1e-6)
+        best = torch.where(hit & (tmin < best), tmin, best)
+
+    cyl = torch.as_tensor(world.cyl, device=dev, dtype=torch.float64)
+    for k in range(cyl.shape[0]):
+        cx, cy, r, h = cyl[k]
+        ox, oy = o[:, 0] - cx, o[:, 1] - cy
+        a = d[:, 0] ** 2 + d[:, 1] ** 2
+        bq = 2 * (ox * d[:, 0] + oy * d[:, 1])
+        cq = ox * ox + oy * oy - r * r
+        disc = bq * bq - 4 * a * cq
+        ok = disc > 0
+        sq = torch.sqrt(torch.clamp(disc, min=0))
+        t = (-bq - sq) / (2 * a.clamp(min=1e-12))
+        z = o[:, 2] + t * d[:, 2]
+        hit = ok & (t > 1e-6) & (z >= 0) & (z <= h)
+        best = torch.where(hit & (t < best), t, best)
+
+    g = torch.Generator(device="cpu").manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
+    noise = torch.randn(n, generator=g, dtype=torch.float64).to(dev) * geo.noise
+    drop = torch.rand(n, generator=g, dtype=torch.float64).to(dev) < geo.dropout
+    rng = best + noise
+    valid = torch.isfinite(best) & (rng < geo.max_range) & ~drop
+    pts = d_s * rng[:, None]
+    pts = torch.where(valid[:, None], pts, torch.zeros_like(pts))
+    out = torch.zeros((n, 4), device=dev, dtype=torch.float32)
+    out[:, :3] = pts.to(torch.float32)
+    return out
+
+
+def make_scan_skewed(config: str = "tiny", k: int = 0, seed: int = SEED, device="cpu", world: World | None = None):
+    """(skewed scan (N,4) float32, mid-sweep pose34, geometry): scan k of the stream with
+    column c cast from trajectory_pose(k + c / cols), the noise and dropout stream of
+    make_scan(config, k).  The pose returned is trajectory_pose(k + 0.5), the frame a
+    deskewed scan is registered in."""
+    geo = GEOMETRIES[config]
+    w = world or World(seed)
+    scan = raycast_skewed(w, lambda s: trajectory_pose(k + s), geo, seed + 7919 * (k + 1), None, device)
+    return scan, trajectory_pose(k + 0.5), geo
+
+
 def default_params(geo: ScanGeometry) -> dict:
     """FORM defaults (extraction.hpp:59-88, matcher.hpp:32-41, ...) for a geometry."""
     return dict(

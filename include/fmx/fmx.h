@@ -277,7 +277,47 @@ fmx_status fmx_register_scan(fmx_ctx* ctx, const float* xyzw, size_t n_points, i
  * withdrawing or replacing call returns only once the staging copy of a withdrawn or
  * replaced pageable scan has finished: from then on its memory is no longer read. */
 fmx_status fmx_next_scan(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device);
-/* Estimator::current_lidar_estimate (form/form.hpp:79). */
+/* ---------------- scan deskewing (no reference counterpart) ------------------
+ * The reference computes the sweep's start and end stamps and never uses them
+ * (python/bindings.cpp:151-152).  Opt-in constant-velocity motion compensation of the
+ * sweep ahead of feature extraction: column c of the organized scan, sampled at sweep
+ * fraction s_c (default c / cols), is moved to the sensor frame at MID-sweep,
+ *   p' = Exp((s_c - 0.5) xi) p,   xi = [w; v] the body-frame twist per scan period
+ * (GTSAM Pose3 tangent order), in fp64, rounded once to fp32; a dropout (x = y = z = 0)
+ * stays 0 and the caller's scan is never written.  The reference fraction 0.5 is fixed:
+ * referred to the sweep start the estimator's own twist feeds back with gain 1.5 and
+ * diverges (DESIGN.md §Scan deskewing).  With deskewing on, fmx_register_scan of scan j uses
+ *   1. the one-shot twist of fmx_deskew_set_twist (IMU / wheel odometry), if one was
+ *      given since the previous registration; else
+ *   2. Log(T_{j-2}^-1 T_{j-1}) of the window's current estimates, if it holds both
+ *      (the two poses predict_next reads, constraints.cpp:71-101); else
+ *   3. initial_twist (scans 0 and 1: a platform that starts at rest passes 0).
+ * The pose estimated for the scan (fmx_current_pose) is then the sensor pose at
+ * mid-sweep, and the features of fmx_extract_download are in that frame.  Never
+ * configured, or enable = 0: every entry point behaves exactly as without this block. */
+typedef struct fmx_deskew_params {
+  int32_t enable;               /* 0 = off */
+  double initial_twist[6];      /* [w; v] per scan period; default 0 */
+  const float* column_fraction; /* cols floats in [0,1], copied; NULL = c/cols */
+} fmx_deskew_params;
+/* Before the first fmx_register_scan of the context (FMX_E_STATE afterwards); a fraction
+ * outside [0,1] or non-finite: FMX_E_INVAL.  Allocates every buffer deskewing needs. */
+fmx_status fmx_deskew_configure(fmx_ctx* ctx, const fmx_deskew_params* p);
+/* One-shot twist for the next fmx_register_scan (overrides the constant-velocity one).
+ * If that scan was announced (fmx_next_scan) and already extracted, the extraction is
+ * dropped and redone in its own fmx_register_scan.  FMX_E_STATE unless deskewing is on. */
+fmx_status fmx_deskew_set_twist(fmx_ctx* ctx, const double twist[6]);
+/* Twist the last fmx_register_scan used; *source = 0 none/off, 1 initial, 2 constant
+ * velocity, 3 caller.  Either pointer may be NULL. */
+fmx_status fmx_deskew_last(fmx_ctx* ctx, double twist[6], int* source);
+/* Stand-alone: deskew one rows*cols scan with a given twist (the same kernel, the
+ * configured column fractions if any); in / out are host or device memory, out must not
+ * alias in (FMX_E_INVAL).  Returns once out is written. */
+fmx_status fmx_deskew(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                      const double twist[6], float* out_xyzw, int dst_on_device);
+
+/* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
+ * pose at the middle of the last registered sweep. */
 fmx_status fmx_current_pose(fmx_ctx* ctx, double pose34[12]);
 /* FORM::map() (python/bindings.cpp:96-119): KeypointMap::to_voxel_map of both feature
  * types (map.tpp:128-146) at the current window estimates, voxel width voxel_width
