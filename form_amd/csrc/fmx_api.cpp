@@ -70,7 +70,8 @@ void match_counts_fetch(fmx_ctx* c, bool wait) {
 // ============================================================================ profiling
 static const char* kProfNames[PROF_COUNT] = {"extract_rows", "closest",   "fit",       "compact", "map_build",
                                              "match",        "pair_sort", "linearize", "insert",  "window",
-                                             "match_linearize", "unpack", "moments", "deskew"};
+                                             "match_linearize", "unpack", "moments", "deskew",
+                                             "organize"};
 
 ProfScope::ProfScope(Prof& p, int i, double by, hipStream_t s) : pr(p), id(i), bytes(by), st(s) {
   if (!pr.on) return;
@@ -477,9 +478,11 @@ const float4* stage_host_scan(fmx_ctx* c, const float* xyzw, size_t n) {
 void pf_drop(fmx_ctx* c);
 // dsk_xi (register_scan with deskewing on): the scan is first moved to mid-sweep by this
 // twist, into the context's buffer on the context stream, and extracted from there; the
-// caller's scan is never written.
+// caller's scan is never written.  dsk_cells (fmx_register_cloud): one sweep fraction per
+// cell of the scan instead of the column table.
 void do_extract(fmx_ctx* c, const float* xyzw, size_t n, uint64_t scan, int on_dev, fmx_feature_counts* out,
-                const std::function<void()>& while_waiting = nullptr, const double* dsk_xi = nullptr) {
+                const std::function<void()>& while_waiting = nullptr, const double* dsk_xi = nullptr,
+                const float* dsk_cells = nullptr) {
   const auto& E = c->P.extraction;
   const size_t R = (size_t)E.num_rows, C = (size_t)E.num_columns;
   if (!xyzw && n) throw StatusError(FMX_E_INVAL, "null scan");
@@ -492,7 +495,8 @@ void do_extract(fmx_ctx* c, const float* xyzw, size_t n, uint64_t scan, int on_d
   const float4* d = on_dev ? reinterpret_cast<const float4*>(xyzw) : stage_host_scan(c, xyzw, n);
   if (dsk_xi) {
     c->dsk.out.ensure(n);  // sized by fmx_deskew_configure: no allocation here
-    run_deskew(c, d, c->dsk.out.p, c->dsk.have_frac ? c->dsk.frac.p : nullptr, (int)R, (int)C, dsk_xi, c->stream);
+    if (dsk_cells) run_deskew_cells(c, d, c->dsk.out.p, dsk_cells, n, dsk_xi, c->stream);
+    else run_deskew(c, d, c->dsk.out.p, c->dsk.have_frac ? c->dsk.frac.p : nullptr, (int)R, (int)C, dsk_xi, c->stream);
     d = c->dsk.out.p;
   }
   run_extract(c, d, (int)R, (int)C, out, while_waiting);
@@ -1390,7 +1394,9 @@ void finish_tail(fmx_ctx* c) {
   if (c->est) finish_tail(c, *c->est);
 }
 
-void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feature_counts* out) {
+// dsk_cells (fmx_register_cloud with deskewing on): the scan's per-cell sweep fractions
+void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feature_counts* out,
+                   const float* dsk_cells = nullptr) {
   HostScope hs_all(0);
   // host time spent outside register_scan since the previous call returned (diagnostic)
   static double last_ret = 0.0;
@@ -1524,7 +1530,7 @@ void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feat
       do_extract(c, xyzw, n, j, on_dev, &fc, [&] {
         map_inputs();
         finish();
-      }, c->dsk.on ? dsk_xi : nullptr);
+      }, c->dsk.on ? dsk_xi : nullptr, dsk_cells);
     }
   }
   std::memcpy(c->dsk.last, dsk_xi, sizeof(dsk_xi));
@@ -1748,6 +1754,18 @@ void fmx_destroy(fmx_ctx* c) {
   c->dsk.pf_out.release();
   c->dsk.io_in.release();
   c->dsk.io_out.release();
+  c->org.ring_to_row.release();
+  c->org.mid.release();
+  c->org.keys.release();
+  c->org.cnt.release();
+  c->org.h_cnt.release();
+  c->org.out[0].release();
+  c->org.out[1].release();
+  c->org.index.release();
+  c->org.frac.release();
+  c->org.in_xyzw.release();
+  c->org.in_ring.release();
+  c->org.in_frac.release();
   for (auto& B : c->scanbuf)
     if (B.p) (void)hipHostFree(B.p);
   for (int t = 0; t < 2; ++t) {
@@ -2260,6 +2278,200 @@ fmx_status fmx_register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev
   return guard<false>(c, [&] {
     drop_match(c);
     register_scan(c, xyzw, n, on_dev, out);
+  });
+}
+
+// ---- unorganized clouds (organize.hip)
+fmx_status fmx_organize_configure(fmx_ctx* c, const fmx_organize_params* p) {
+  return guard<false>(c, [&] {
+    if (!p) throw StatusError(FMX_E_INVAL, "null organize parameters");
+    if (c->est) throw StatusError(FMX_E_STATE, "fmx_organize_configure after the first registration");
+    const auto& E = c->P.extraction;
+    if (E.num_rows <= 0 || E.num_columns <= 0) throw StatusError(FMX_E_INVAL, "no scan geometry");
+    const size_t R = (size_t)E.num_rows, cells = R * (size_t)E.num_columns;
+    if (cells >= 0xFFFFFFFFull) throw StatusError(FMX_E_INVAL, "scan geometry too large");
+    if (p->row_source != FMX_ROW_RING && p->row_source != FMX_ROW_ELEVATION)
+      throw StatusError(FMX_E_INVAL, "unknown row source");
+    if (!std::isfinite(p->azimuth_offset)) throw StatusError(FMX_E_INVAL, "non-finite azimuth offset");
+    const bool elev = p->row_source == FMX_ROW_ELEVATION;
+    // elevation mode: the rows - 1 midpoints and the outer limits, negated when the table
+    // descends so that they ascend with the row index (the kernel negates the angle too)
+    std::vector<double> mid;
+    double sign = 1.0, lo = -HUGE_VAL, hi = HUGE_VAL;
+    if (elev) {
+      const double* t = p->elevation;
+      if (!t) throw StatusError(FMX_E_INVAL, "elevation mode without an elevation table");
+      for (size_t k = 0; k < R; ++k)
+        if (!std::isfinite(t[k])) throw StatusError(FMX_E_INVAL, "non-finite elevation " + std::to_string(k));
+      if (R > 1) {
+        sign = t[1] > t[0] ? 1.0 : -1.0;
+        for (size_t k = 0; k + 1 < R; ++k)
+          if (!(sign * t[k + 1] > sign * t[k]))
+            throw StatusError(FMX_E_INVAL, "elevation table is not strictly monotonic at " + std::to_string(k + 1));
+        mid.resize(R - 1);
+        for (size_t k = 0; k + 1 < R; ++k) mid[k] = sign * (0.5 * (t[k] + t[k + 1]));
+        lo = sign * t[0] - 0.5 * (sign * t[1] - sign * t[0]);
+        hi = sign * t[R - 1] + 0.5 * (sign * t[R - 1] - sign * t[R - 2]);
+      }
+    } else if (p->ring_to_row) {
+      for (uint32_t k = 0; k < p->n_rings; ++k)
+        if (p->ring_to_row[k] < -1 || p->ring_to_row[k] >= (int32_t)R)
+          throw StatusError(FMX_E_INVAL, "ring_to_row entry " + std::to_string(k) + " is not a row or -1");
+    }
+    sync_all(c);  // an earlier fmx_organize may still read the tables
+    auto& o = c->org;
+    o.elevation = elev;
+    o.clockwise = p->clockwise != 0;
+    o.az_off = p->azimuth_offset;
+    o.sign = sign;
+    o.lo = lo;
+    o.hi = hi;
+    if (!mid.empty()) {
+      o.mid.ensure(mid.size());
+      FMX_HIP(hipMemcpy(o.mid.p, mid.data(), mid.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    o.have_ring_map = !elev && p->ring_to_row != nullptr;
+    o.n_rings = o.have_ring_map ? p->n_rings : 0;
+    if (o.have_ring_map && o.n_rings) {
+      o.ring_to_row.ensure(o.n_rings);
+      FMX_HIP(hipMemcpy(o.ring_to_row.p, p->ring_to_row, o.n_rings * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    o.on = p->enable != 0;
+    if (o.on) {  // every per-scan buffer now: a registration allocates nothing for the stage
+      o.keys.ensure(cells);
+      // the only clearing pass; on the context stream, which the claims are ordered behind
+      // (a plain hipMemset is not ordered with a non-blocking stream)
+      FMX_HIP(hipMemsetAsync(o.keys.p, 0xFF, o.keys.cap * sizeof(unsigned long long), c->stream));
+      o.cnt.ensure(4);
+      FMX_HIP(hipMemsetAsync(o.cnt.p, 0, 4 * sizeof(uint32_t), c->stream));
+      o.h_cnt.ensure(4);
+      std::memset(o.h_cnt.p, 0, 4 * sizeof(uint32_t));
+      o.out[0].ensure(cells);
+      o.out[1].ensure(cells);
+      o.index.ensure(cells);
+      o.frac.ensure(cells);
+      o.in_xyzw.ensure(cells);  // DBuf holds twice what is asked for: clouds of up to 2 * rows * cols points
+      o.in_ring.ensure(cells);
+      o.in_frac.ensure(cells);
+    }
+  });
+}
+
+namespace {
+// Validate the cloud, bring a host cloud to the device and queue claim + gather into d_out
+// (+ the context's index and fraction planes) on the context stream.  Returns the
+// per-cell fraction plane, or null for a cloud without fractions.
+const float* organize_cloud(fmx_ctx* c, const fmx_cloud* cl, float4* d_out) {
+  auto& o = c->org;
+  if (!o.on) throw StatusError(FMX_E_STATE, "the organizer is not enabled (fmx_organize_configure)");
+  if (!cl) throw StatusError(FMX_E_INVAL, "null cloud");
+  const size_t n = cl->n;
+  if ((unsigned long long)n >= (1ull << 32)) throw StatusError(FMX_E_INVAL, "a cloud holds fewer than 2^32 points");
+  if (n == 0 && (cl->xyzw || cl->ring || cl->sweep_fraction))
+    throw StatusError(FMX_E_INVAL, "an empty cloud with non-null arrays");
+  if (n && !cl->xyzw) throw StatusError(FMX_E_INVAL, "null cloud points");
+  if (n && !o.elevation && !cl->ring) throw StatusError(FMX_E_INVAL, "ring mode needs the cloud's ring indices");
+  const float4* d_pts = reinterpret_cast<const float4*>(cl->xyzw);
+  const uint16_t* d_ring = o.elevation ? nullptr : cl->ring;
+  const float* d_frac = cl->sweep_fraction;
+  if (n && !cl->on_device) {
+    o.in_xyzw.ensure(n);
+    FMX_HIP(hipMemcpyAsync(o.in_xyzw.p, cl->xyzw, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    d_pts = o.in_xyzw.p;
+    if (d_ring) {
+      o.in_ring.ensure(n);
+      FMX_HIP(hipMemcpyAsync(o.in_ring.p, cl->ring, n * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+      d_ring = o.in_ring.p;
+    }
+    if (d_frac) {
+      o.in_frac.ensure(n);
+      FMX_HIP(hipMemcpyAsync(o.in_frac.p, cl->sweep_fraction, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+      d_frac = o.in_frac.p;
+    }
+  }
+  run_organize(c, d_pts, d_ring, d_frac, n, d_out, o.index.p, o.frac.p, c->stream);
+  return d_frac ? o.frac.p : nullptr;
+}
+void organize_counts_read(const fmx_ctx* c, fmx_organize_counts* out) {
+  const uint32_t* h = c->org.h_cnt.p;
+  out->placed = h[0];
+  out->displaced = h[1];
+  out->off_grid = h[2];
+  out->invalid = h[3];
+}
+}  // namespace
+
+fmx_status fmx_organize(fmx_ctx* c, const fmx_cloud* cloud, float* out_xyzw, int dst_on_dev, uint32_t* out_index,
+                        float* out_fraction, fmx_organize_counts* counts) {
+  return guard<false>(c, [&] {
+    auto& o = c->org;
+    const auto& E = c->P.extraction;
+    const size_t cells = (size_t)(E.num_rows > 0 ? E.num_rows : 0) * (size_t)(E.num_columns > 0 ? E.num_columns : 0);
+    // straight into the caller's device scan; else into the buffer the next fmx_register_cloud overwrites
+    float4* d_out = out_xyzw && dst_on_dev ? reinterpret_cast<float4*>(out_xyzw) : o.out[o.next].p;
+    const float* fr = organize_cloud(c, cloud, d_out);
+    const hipMemcpyKind kind = dst_on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (out_xyzw && !dst_on_dev)
+      FMX_HIP(hipMemcpyAsync(out_xyzw, d_out, cells * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (out_index) FMX_HIP(hipMemcpyAsync(out_index, o.index.p, cells * sizeof(uint32_t), kind, c->stream));
+    if (out_fraction && fr) FMX_HIP(hipMemcpyAsync(out_fraction, fr, cells * sizeof(float), kind, c->stream));
+    FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns the cloud and the outputs again
+    if (counts) organize_counts_read(c, counts);
+  });
+}
+
+fmx_status fmx_register_cloud(fmx_ctx* c, const fmx_cloud* cloud, fmx_feature_counts* out,
+                              fmx_organize_counts* organize_counts) {
+  return guard<false>(c, [&] {
+    drop_match(c);
+    auto& o = c->org;
+    const auto& E = c->P.extraction;
+    float4* d = o.out[o.next].p;
+    const float* fr = organize_cloud(c, cloud, d);
+    o.next ^= 1;
+    // the gather is queued on the context stream ahead of the extraction register_scan
+    // waits for: the host copies of a host cloud are consumed, and the counts are in,
+    // by the time it returns
+    register_scan(c, reinterpret_cast<const float*>(d), (size_t)E.num_rows * (size_t)E.num_columns, 1, out,
+                  c->dsk.on ? fr : nullptr);
+    if (organize_counts) organize_counts_read(c, organize_counts);
+  });
+}
+
+fmx_status fmx_deskew_cells(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const float* fraction,
+                            const double twist[6], float* out, int dst_on_dev) {
+  return guard<false>(c, [&] {
+    const auto& E = c->P.extraction;
+    const size_t R = (size_t)(E.num_rows > 0 ? E.num_rows : 0), C = (size_t)(E.num_columns > 0 ? E.num_columns : 0);
+    if (!xyzw || !out || !twist || !fraction) throw StatusError(FMX_E_INVAL, "null scan / fractions / output / twist");
+    if (n == 0 || n != R * C)
+      throw StatusError(FMX_E_SIZE, "Provided scan does not match the expected size " + std::to_string(R * C) +
+                                        " != " + std::to_string(n));
+    for (int k = 0; k < 6; ++k)
+      if (!std::isfinite(twist[k])) throw StatusError(FMX_E_INVAL, "non-finite twist");
+    if ((src_on_dev != 0) == (dst_on_dev != 0)) {  // same memory kind: the ranges must not overlap
+      const uintptr_t a = reinterpret_cast<uintptr_t>(xyzw), b = reinterpret_cast<uintptr_t>(out);
+      const uintptr_t bytes = n * sizeof(float4);
+      if (a < b + bytes && b < a + bytes) throw StatusError(FMX_E_INVAL, "fmx_deskew_cells: out aliases in");
+    }
+    const float4* d_in = reinterpret_cast<const float4*>(xyzw);
+    const float* d_fr = fraction;
+    float4* d_out = reinterpret_cast<float4*>(out);
+    if (!src_on_dev) {
+      c->dsk.io_in.ensure(n);
+      c->org.in_frac.ensure(n);
+      FMX_HIP(hipMemcpyAsync(c->dsk.io_in.p, xyzw, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+      FMX_HIP(hipMemcpyAsync(c->org.in_frac.p, fraction, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+      d_in = c->dsk.io_in.p;
+      d_fr = c->org.in_frac.p;
+    }
+    if (!dst_on_dev) {
+      c->dsk.io_out.ensure(n);
+      d_out = c->dsk.io_out.p;
+    }
+    run_deskew_cells(c, d_in, d_out, d_fr, n, twist, c->stream);
+    if (!dst_on_dev) FMX_HIP(hipMemcpyAsync(out, d_out, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns in / out again
   });
 }
 

@@ -133,6 +133,7 @@ enum ProfId {
   PROF_UNPACK,
   PROF_MOMENTS,
   PROF_DESKEW,
+  PROF_ORGANIZE,
   PROF_COUNT
 };
 
@@ -412,6 +413,30 @@ struct fmx_ctx {
     double pf_twist[6] = {};       // ... what the queued extraction used
     int pf_src = 0;
   } dsk;
+
+  // ---- unorganized clouds (organize.hip; fmx_organize_configure).  Off unless configured:
+  // no buffer below is then allocated and no entry point behaves differently.
+  struct Organize {
+    bool on = false;
+    bool elevation = false;        // row from the elevation table (else from the ring)
+    bool clockwise = false;
+    double az_off = 0.0;
+    bool have_ring_map = false;
+    uint32_t n_rings = 0;
+    fmx::DBuf<int32_t> ring_to_row;
+    fmx::DBuf<double> mid;         // elevation mode: rows - 1 midpoints, ascending with the row
+    double lo = 0.0, hi = 0.0, sign = 1.0;  // ... the table's outer limits; -1: the table descends
+    fmx::DBuf<unsigned long long> keys;     // rows * cols claim keys, all-ones between scans
+    fmx::DBuf<uint32_t> cnt;       // {invalid, off_grid, gather ticket (2 words)}, 0 between scans
+    fmx::HBuf<uint32_t> h_cnt;     // {placed, displaced, off_grid, invalid} of the last gather
+    fmx::DBuf<float4> out[2];      // fmx_register_cloud's organized scans, in rotation
+    int next = 0;
+    fmx::DBuf<uint32_t> index;     // per cell: the winner's input index
+    fmx::DBuf<float> frac;         // per cell: the winner's sweep fraction
+    fmx::DBuf<float4> in_xyzw;     // device copies of a host cloud
+    fmx::DBuf<uint16_t> in_ring;
+    fmx::DBuf<float> in_frac;
+  } org;
 
   // ---- window keypoint store + maps
   fmx::Pool pool[2];
@@ -791,6 +816,14 @@ void run_extract(fmx_ctx* c, const float4* d_scan, int R, int C, fmx_feature_cou
 // twist xi; d_frac: C per-column sweep fractions, or null for c / C
 void run_deskew(fmx_ctx* c, const float4* d_in, float4* d_out, const float* d_frac, int R, int C,
                 const double xi[6], hipStream_t st);
+// ... with one sweep fraction per cell (n = R * C floats: an organized cloud's plane)
+void run_deskew_cells(fmx_ctx* c, const float4* d_in, float4* d_out, const float* d_cell_frac, size_t n,
+                      const double xi[6], hipStream_t st);
+// organize.hip: n unordered points (d_ring in ring mode, d_frac or null) -> the organized
+// scan, winner index and sweep fraction of each of the R * C cells (d_frac_out unused
+// without d_frac), claim + gather on stream st; the counts reach c->org.h_cnt
+void run_organize(fmx_ctx* c, const float4* d_pts, const uint16_t* d_ring, const float* d_frac, size_t n,
+                  float4* d_out, uint32_t* d_index, float* d_frac_out, hipStream_t st);
 // packed x, y, z (a staged host scan) -> float4 points with pad 0, on stream st
 void unpack_xyz(fmx_ctx* c, const float* d_packed, float4* d_out, size_t n, hipStream_t st);
 // st: stream to build on (default the context stream; register_scan uses the side

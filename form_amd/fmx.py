@@ -60,6 +60,24 @@ class _DeskewParams(C.Structure):
     _fields_ = [("enable", C.c_int32), ("initial_twist", C.c_double * 6), ("column_fraction", C.c_void_p)]
 
 
+class _OrganizeParams(C.Structure):
+    _fields_ = [("enable", C.c_int32), ("row_source", C.c_int32), ("elevation", C.c_void_p),
+                ("ring_to_row", C.c_void_p), ("n_rings", C.c_uint32), ("azimuth_offset", C.c_double),
+                ("clockwise", C.c_int32)]
+
+
+class _Cloud(C.Structure):
+    _fields_ = [("xyzw", C.c_void_p), ("n", C.c_size_t), ("ring", C.c_void_p), ("sweep_fraction", C.c_void_p),
+                ("on_device", C.c_int32)]
+
+
+class _OrganizeCounts(C.Structure):
+    _fields_ = [("placed", C.c_uint32), ("displaced", C.c_uint32), ("off_grid", C.c_uint32), ("invalid", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(placed=self.placed, displaced=self.displaced, off_grid=self.off_grid, invalid=self.invalid)
+
+
 class _Counts(C.Structure):
     _fields_ = [("planar", C.c_uint32), ("point", C.c_uint32), ("planar_selected", C.c_uint32)]
 
@@ -89,11 +107,17 @@ EXPORTED = [
     "fmx_map_download", "fmx_register_points", "fmx_scan_buffer", "fmx_match_cert", "fmx_profile_match_work",
     "fmx_corr_generation", "fmx_moments", "fmx_moments_contract",
     "fmx_deskew_configure", "fmx_deskew_set_twist", "fmx_deskew_last", "fmx_deskew",
+    "fmx_organize_configure", "fmx_organize", "fmx_register_cloud", "fmx_deskew_cells",
 ]
 
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _host(a):
+    """A host array of a numpy array or CPU tensor."""
+    return a.numpy() if hasattr(a, "numpy") and not isinstance(a, np.ndarray) else a
 
 
 def _ready(*tensors):
@@ -436,6 +460,138 @@ class Context:
         del keep
         return res
 
+    def deskew_cells(self, scan, fraction, twist, out=None):
+        """fmx_deskew_cells: as deskew, with one sweep fraction per point of the rows * cols
+        scan ((N,) float32, host or device like the scan) instead of one per column."""
+        on_dev, ptr, n, keep = _scan_ptr(scan)
+        xi = np.ascontiguousarray(twist, np.float64).reshape(6)
+        if on_dev:
+            import torch
+            fr = torch.as_tensor(fraction, dtype=torch.float32, device=keep.device).reshape(-1).contiguous()
+            res = torch.empty_like(keep) if out is None else out
+            if not (res.is_cuda and res.is_contiguous() and res.dtype == keep.dtype and res.shape == keep.shape):
+                raise ValueError("out must be a contiguous (N, 4) float32 CUDA tensor")
+            _ready(keep, fr, res)
+            fptr, optr = C.c_void_p(fr.data_ptr()), C.c_void_p(res.data_ptr())
+        else:
+            fr = np.ascontiguousarray(_host(fraction), np.float32).reshape(-1)
+            res = np.empty((n, 4), np.float32) if out is None else out
+            if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (n, 4)
+                    and res.flags.c_contiguous):
+                raise ValueError("out must be a contiguous (N, 4) float32 array")
+            fptr, optr = _p(fr), _p(res)
+        if len(fr) != n:
+            raise ValueError("deskew_cells needs one fraction per point")
+        self._chk(self._L.fmx_deskew_cells(self.h, ptr, C.c_size_t(n), C.c_int(on_dev), fptr, _p(xi), optr,
+                                           C.c_int(on_dev)))
+        del keep, fr
+        return res
+
+    # ---------------------------------------------------------------- unorganized clouds
+    def organize_configure(self, enable: bool = True, elevation=None, ring_to_row=None,
+                           azimuth_offset: float = 0.0, clockwise: bool = False):
+        """fmx_organize_configure (before the first registration): accept unordered clouds.
+        elevation: rows angles in radians, strictly monotonic -> elevation mode; else ring
+        mode with row = ring_to_row[ring] (None: identity).  azimuth_offset: the azimuth of
+        the centre of column 0."""
+        p = _OrganizeParams()
+        p.enable = int(bool(enable))
+        p.azimuth_offset = float(azimuth_offset)
+        p.clockwise = int(bool(clockwise))
+        el = r2r = None
+        if elevation is not None:
+            el = np.ascontiguousarray(elevation, np.float64).reshape(-1)
+            if len(el) != self.params.extraction.num_rows:
+                raise ValueError("elevation needs one angle per scan row")
+            p.row_source = 1
+            p.elevation = el.ctypes.data
+        elif ring_to_row is not None:
+            r2r = np.ascontiguousarray(ring_to_row, np.int32).reshape(-1)
+            p.ring_to_row = r2r.ctypes.data
+            p.n_rings = len(r2r)
+        self._chk(self._L.fmx_organize_configure(self.h, C.byref(p)))
+        del el, r2r
+
+    def _cloud(self, xyzw, ring, sweep_fraction):
+        """(fmx_cloud, keepalive) of numpy arrays or torch tensors: (N, 4) float32 points,
+        (N,) uint16 rings and (N,) float32 sweep fractions (either may be None), all host
+        or all device like the points."""
+        on_dev, ptr, n, keep = _scan_ptr(xyzw)
+        cl = _Cloud()
+        cl.n = n
+        cl.on_device = on_dev
+        keeps = [keep]
+        if n == 0:  # an empty cloud carries no arrays
+            return cl, keeps
+        cl.xyzw = ptr
+        if on_dev:
+            import torch
+            if ring is not None:
+                # 16-bit rings travel as int16 (the same bits): torch's uint16 support is thin
+                if isinstance(ring, np.ndarray):
+                    ring = torch.from_numpy(np.ascontiguousarray(ring, np.uint16).view(np.int16))
+                r = ring if ring.dtype in (torch.int16, torch.uint16) else ring.to(torch.int16)
+                r = r.to(keep.device).reshape(-1).contiguous()
+                keeps.append(r)
+                cl.ring = r.data_ptr()
+            if sweep_fraction is not None:
+                f = torch.as_tensor(sweep_fraction, dtype=torch.float32, device=keep.device).reshape(-1).contiguous()
+                keeps.append(f)
+                cl.sweep_fraction = f.data_ptr()
+            _ready(*keeps)
+        else:
+            if ring is not None:
+                r = np.ascontiguousarray(_host(ring), np.uint16).reshape(-1)
+                keeps.append(r)
+                cl.ring = r.ctypes.data
+            if sweep_fraction is not None:
+                f = np.ascontiguousarray(_host(sweep_fraction), np.float32).reshape(-1)
+                keeps.append(f)
+                cl.sweep_fraction = f.ctypes.data
+        if any(len(k) != n for k in keeps[1:]):
+            raise ValueError("ring and sweep_fraction need one value per point")
+        return cl, keeps
+
+    def organize(self, xyzw, ring=None, sweep_fraction=None):
+        """fmx_organize: (scan (rows * cols, 4) float32, index (rows * cols,) uint32,
+        fraction (rows * cols,) float32 or None without sweep fractions, counts dict) of
+        one cloud.  Device tensors give device tensors (the index as int64), host input
+        gives numpy arrays."""
+        cl, keeps = self._cloud(xyzw, ring, sweep_fraction)
+        e = self.params.extraction
+        cells = e.num_rows * e.num_columns
+        have_f = sweep_fraction is not None and cl.n > 0
+        cnt = _OrganizeCounts()
+        if cl.on_device:
+            import torch
+            dev = keeps[0].device
+            scan = torch.empty((cells, 4), dtype=torch.float32, device=dev)
+            idx = torch.empty(cells, dtype=torch.int32, device=dev)
+            fr = torch.empty(cells, dtype=torch.float32, device=dev) if have_f else None
+            ptrs = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (scan, idx, fr)]
+        else:
+            scan = np.empty((cells, 4), np.float32)
+            idx = np.empty(cells, np.uint32)
+            fr = np.empty(cells, np.float32) if have_f else None
+            ptrs = [_p(scan), _p(idx), _p(fr)]
+        self._chk(self._L.fmx_organize(self.h, C.byref(cl), ptrs[0], C.c_int(cl.on_device), ptrs[1], ptrs[2],
+                                       C.byref(cnt)))
+        del keeps
+        if cl.on_device:
+            idx = idx.to(torch.int64) & 0xFFFFFFFF
+        return scan, idx, fr, cnt.as_dict()
+
+    def register_cloud(self, xyzw, ring=None, sweep_fraction=None):
+        """fmx_register_cloud: organize the cloud on the device and register it.  Returns
+        (planar, point, organize counts dict)."""
+        cl, keeps = self._cloud(xyzw, ring, sweep_fraction)
+        c = _Counts()
+        cnt = _OrganizeCounts()
+        self._chk(self._L.fmx_register_cloud(self.h, C.byref(cl), C.byref(c), C.byref(cnt)))
+        del keeps
+        self.n_planar, self.n_point = c.planar, c.point
+        return c.planar, c.point, cnt.as_dict()
+
     def current_pose(self) -> np.ndarray:
         T = np.zeros(12)
         self._chk(self._L.fmx_current_pose(self.h, _p(T)))
@@ -661,6 +817,31 @@ def _points_xyz(mm) -> np.ndarray:
     return np.array([[p.x, p.y, p.z] for p in pts], np.float64).reshape(-1, 3)
 
 
+def _seconds(t) -> float:
+    """A time as float seconds: a number or an evalio Duration (to_sec)."""
+    return float(t.to_sec()) if hasattr(t, "to_sec") else float(t)
+
+
+def _cloud_fields(mm):
+    """A LidarMeasurement's points as an unordered cloud: ((N, 3) xyz, (N,) ring or None,
+    (N,) time in seconds or None) from an (N, >= 5) array (columns 3 and 4: ring, time),
+    an (N, 3..4) array (no ring, no time), or evalio-style points (x, y, z, row, t)."""
+    pts = getattr(mm, "points", mm)
+    try:
+        a = np.asarray(pts, np.float64)
+        if a.ndim == 2 and a.shape[1] >= 3:
+            if a.shape[1] >= 5:
+                return a[:, :3], a[:, 3].astype(np.uint16), a[:, 4]
+            return a[:, :3], None, None
+    except (TypeError, ValueError):
+        pass
+    pts = list(pts)
+    xyz = np.array([[p.x, p.y, p.z] for p in pts], np.float64).reshape(-1, 3)
+    ring = np.array([p.row for p in pts], np.uint16) if pts and hasattr(pts[0], "row") else None
+    t = np.array([_seconds(p.t) for p in pts], np.float64) if pts and hasattr(pts[0], "t") else None
+    return xyz, ring, t
+
+
 class FORM:
     """form._core.FORM (bindings.cpp:48-180) on the MI355X path.
 
@@ -681,6 +862,8 @@ class FORM:
         self._scan = -1
         self._pose = np.eye(4)
         self._deskew = None  # set_deskew's arguments, applied by initialize()
+        self._organize = None  # set_organize's arguments, applied by initialize()
+        self._scan_period = None  # seconds, from set_lidar_params when the parameters carry one
 
     @staticmethod
     def name() -> str:
@@ -734,6 +917,12 @@ class FORM:
         e.max_norm_squared = float(params.max_range) * float(params.max_range)
         e.num_columns = int(params.num_columns)
         e.num_rows = int(params.num_rows)
+        # bindings.cpp:131: delta_time_ = params.delta_time() (evalio: 1 / rate)
+        if hasattr(params, "delta_time"):
+            dt = params.delta_time
+            self._scan_period = _seconds(dt() if callable(dt) else dt)
+        elif getattr(params, "rate", None):
+            self._scan_period = 1.0 / float(params.rate)
 
     def set_imu_T_lidar(self, T) -> None:
         """bindings.cpp:135-137: lidar_T_imu = (imu_T_lidar)^-1."""
@@ -746,6 +935,8 @@ class FORM:
         self._est = Context(self.params, self.device)
         if self._deskew is not None:
             self._est.deskew_configure(*self._deskew)
+        if self._organize is not None:
+            self._est.organize_configure(**self._organize)
         self._scan = -1
         self._pose = np.eye(4)
 
@@ -758,6 +949,17 @@ class FORM:
                         None if initial_twist is None else np.array(initial_twist, np.float64).reshape(6),
                         None if column_fraction is None else np.array(column_fraction, np.float32).reshape(-1))
 
+    def set_organize(self, enable: bool = True, elevation=None, ring_to_row=None, azimuth_offset: float = 0.0,
+                     clockwise: bool = False) -> None:
+        """Accept unordered clouds of any length in add_lidar (fmx_organize_configure; no
+        reference counterpart, so not a pipeline YAML key).  Applied by initialize().
+        elevation: rows angles in radians (elevation mode); else the points' ring picks the
+        row, through ring_to_row if given."""
+        self._organize = dict(enable=bool(enable),
+                              elevation=None if elevation is None else np.array(elevation, np.float64).reshape(-1),
+                              ring_to_row=None if ring_to_row is None else np.array(ring_to_row, np.int32).reshape(-1),
+                              azimuth_offset=float(azimuth_offset), clockwise=bool(clockwise))
+
     def add_imu(self, mm) -> None:  # bindings.cpp:144 (unused)
         pass
 
@@ -766,6 +968,8 @@ class FORM:
         (current_lidar_estimate * lidar_T_imu) and return its features."""
         if self._est is None:
             raise RuntimeError("FORM.add_lidar before initialize()")
+        if self._organize is not None and self._organize["enable"]:
+            return self._add_cloud(mm)
         xyz = _points_xyz(mm)
         # point_to_form: PointXYZf(x, y, z) (bindings.cpp:43-45), assembled straight into
         # a pinned fmx_scan_buffer: the registration then DMAs it with no staging copy
@@ -773,6 +977,23 @@ class FORM:
         scan[:, :3] = xyz
         scan[:, 3] = 0.0
         self._est.register_scan(scan)
+        return self._scan_done()
+
+    def _add_cloud(self, mm) -> dict:
+        """add_lidar with set_organize: a measurement of any length, organized on the
+        device.  Ring and time come from an (N, >= 5) array (columns 3 and 4) or from
+        evalio-style points (row, t); times become sweep fractions with the scan period of
+        set_lidar_params (without one they are taken as fractions already)."""
+        xyz, ring, t = _cloud_fields(mm)
+        cloud = np.zeros((len(xyz), 4), np.float32)
+        cloud[:, :3] = xyz
+        frac = None
+        if t is not None:
+            frac = (t / self._scan_period if self._scan_period else t).astype(np.float32)
+        self._est.register_cloud(cloud, ring, frac)
+        return self._scan_done()
+
+    def _scan_done(self) -> dict:
         self._scan += 1
         self._pose = _pose44(self._est.current_pose()) @ self.lidar_T_imu
         d = self._est.extract_download()

@@ -264,6 +264,28 @@ def make_scan_skewed(config: str = "tiny", k: int = 0, seed: int = SEED, device=
     return scan, trajectory_pose(k + 0.5), geo
 
 
+def elevation_table(geo: ScanGeometry) -> np.ndarray:
+    """The rows' elevations in radians (row 0 highest), as _ray_dirs spreads them."""
+    return torch.linspace(math.radians(geo.elev_deg), -math.radians(geo.elev_deg), geo.rows,
+                          dtype=torch.float64).numpy()
+
+
+def to_cloud(scan, geo: ScanGeometry, seed: int, fractions=None):
+    """An organized scan as a sensor driver would deliver it: the dropouts removed and the
+    returns in a seeded random order.  Returns (xyzw (n, 4) float32, ring (n,) uint16: the
+    row, sweep_fraction (n,) float32: float32(c / cols) of the point's column, or the value
+    of its cell in `fractions` (rows * cols)) as numpy arrays."""
+    a = scan.cpu().numpy() if isinstance(scan, torch.Tensor) else np.asarray(scan)
+    a = np.ascontiguousarray(a, np.float32).reshape(geo.rows * geo.cols, 4)
+    keep = np.flatnonzero(a[:, :3].any(1))
+    keep = keep[np.random.default_rng(seed).permutation(len(keep))]
+    if fractions is None:
+        frac = ((keep % geo.cols).astype(np.float64) / geo.cols).astype(np.float32)
+    else:
+        frac = np.asarray(fractions, np.float32).reshape(-1)[keep]
+    return a[keep].copy(), (keep // geo.cols).astype(np.uint16), frac
+
+
 def default_params(geo: ScanGeometry) -> dict:
     """FORM defaults (extraction.hpp:59-88, matcher.hpp:32-41, ...) for a geometry."""
     return dict(

@@ -316,6 +316,82 @@ fmx_status fmx_deskew_last(fmx_ctx* ctx, double twist[6], int* source);
 fmx_status fmx_deskew(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
                       const double twist[6], float* out_xyzw, int dst_on_device);
 
+/* ---------------- unorganized clouds (no reference counterpart) --------------
+ * The reference copies the measurement's points in order and hands them to the estimator
+ * as the organized scan (python/bindings.cpp:150-156): evalio delivers rows*cols points,
+ * row-major, with zeros for missing returns.  A sensor driver (Velodyne, Hesai, a ROS
+ * PointCloud2) delivers an unordered list of returns instead, each with a ring index and
+ * a time.  Opt-in stage "cloud in, organized device scan out", ahead of the unchanged
+ * pipeline (DESIGN.md §Unorganized clouds).  For each point, all in fp64 on the fp32
+ * coordinates:
+ *   skipped (counted invalid) when x, y or z is not finite or x = y = z = 0;
+ *   u = (atan2(y, x) - azimuth_offset) * cols / 2pi, negated when clockwise;
+ *   col = floor(u + 0.5) mod cols (column c is centred on azimuth c * 2pi / cols);
+ *   row = ring_to_row[ring] (identity without a table; a ring at or past the table, or
+ *         mapped to -1: off-grid), or, in elevation mode, the table entry nearest to
+ *         atan2(z, sqrt(x*x + y*y)), a tie to the lower row, off-grid when beyond an
+ *         outermost entry by more than half the spacing to that entry's neighbour.
+ * Of the points of one cell the one with the smallest r2 = (x*x + y*y) + z*z (fp32, that
+ * order, no contraction) stays, the lowest input index among equal r2; the others count
+ * as displaced.  The result does not depend on the order the device's threads run in.
+ * Never configured, or enable = 0: every other entry point behaves exactly as without
+ * this block. */
+typedef enum fmx_row_source { FMX_ROW_RING = 0, FMX_ROW_ELEVATION = 1 } fmx_row_source;
+typedef struct fmx_organize_params {
+  int32_t enable;             /* 0 = off */
+  int32_t row_source;         /* fmx_row_source */
+  const double* elevation;    /* elevation mode: rows angles in radians, strictly monotonic, copied */
+  const int32_t* ring_to_row; /* ring mode: n_rings rows (-1 = off-grid), copied; NULL = identity */
+  uint32_t n_rings;
+  double azimuth_offset;      /* azimuth of the centre of column 0, radians */
+  int32_t clockwise;          /* 1: columns count clockwise (seen from above) */
+} fmx_organize_params;
+/* rows and cols are the context's extraction parameters.  Before the first registration of
+ * the context (FMX_E_STATE afterwards).  FMX_E_INVAL: an elevation table that is not
+ * strictly monotonic or holds a non-finite value, elevation mode without a table, a
+ * ring_to_row entry >= rows (or < -1), a non-finite offset.  Allocates every buffer the
+ * stage needs, sized for clouds of up to 2 * rows * cols points (a larger cloud grows the
+ * device copies of a host cloud once). */
+fmx_status fmx_organize_configure(fmx_ctx* ctx, const fmx_organize_params* p);
+typedef struct fmx_cloud {
+  const float* xyzw;           /* n * (x, y, z, pad) */
+  size_t n;
+  const uint16_t* ring;        /* n ring indices; required in ring mode, else may be NULL */
+  const float* sweep_fraction; /* n sweep fractions in [0,1] (clamped), or NULL */
+  int32_t on_device;           /* all three arrays in device (1) or host (0) memory */
+} fmx_cloud;
+typedef struct fmx_organize_counts {
+  uint32_t placed;    /* cells filled */
+  uint32_t displaced; /* lost their cell to a nearer (or equal and earlier) point */
+  uint32_t off_grid;
+  uint32_t invalid;   /* the four sum to n */
+} fmx_organize_counts;
+/* Stand-alone: organize one cloud.  out_xyzw: rows*cols points, winners copied bit for bit
+ * with pad 0, empty cells all 0; out_index: per cell the winner's input index, 0xFFFFFFFF
+ * for an empty cell; out_fraction: per cell the winner's sweep fraction, 0 for an empty
+ * cell (left unwritten when the cloud has none).  The three outputs are device memory when
+ * dst_on_device, else host memory; any of them and counts may be NULL.  Returns once they
+ * are written.  FMX_E_STATE unless the stage is configured and enabled; FMX_E_INVAL for a
+ * NULL cloud, ring = NULL in ring mode, n >= 2^32, n = 0 with a non-NULL array, n > 0
+ * with xyzw = NULL. */
+fmx_status fmx_organize(fmx_ctx* ctx, const fmx_cloud* cloud, float* out_xyzw, int dst_on_device,
+                        uint32_t* out_index, float* out_fraction, fmx_organize_counts* counts);
+/* Organize the cloud into the context's next device buffer (two in rotation), then exactly
+ * fmx_register_scan of that buffer with src_on_device = 1.  With deskewing on and
+ * sweep_fraction given, every point is deskewed with its own fraction (the per-cell plane);
+ * without fractions, with the configured column table or c / cols.  Twist selection,
+ * fmx_deskew_last, fmx_current_pose and fmx_last_stats as for fmx_register_scan.  A scan
+ * announced with fmx_next_scan is the documented pointer mismatch: its queued extraction
+ * is discarded.  Clouds cannot be announced ahead of time (the organizer is not
+ * pipelined).  Either counts pointer may be NULL. */
+fmx_status fmx_register_cloud(fmx_ctx* ctx, const fmx_cloud* cloud, fmx_feature_counts* feature_counts,
+                              fmx_organize_counts* organize_counts);
+/* Stand-alone: fmx_deskew with one sweep fraction per point of the rows*cols scan
+ * (fraction: n_points floats in [0,1], in the memory kind of xyzw) instead of one
+ * per column; equal fractions give fmx_deskew's bits.  Needs no configuration. */
+fmx_status fmx_deskew_cells(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                            const float* fraction, const double twist[6], float* out_xyzw, int dst_on_device);
+
 /* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
  * pose at the middle of the last registered sweep. */
 fmx_status fmx_current_pose(fmx_ctx* ctx, double pose34[12]);
