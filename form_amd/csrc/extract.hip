@@ -22,6 +22,7 @@
 // were exact too, but curvature is monotone along smooth surfaces, so the rounds
 // chained ~pps/k deep.)  Sectors stay sequential: the suppression of sector s
 // spills into sector s+1 (parity hazard 5).
+#include "extract_plan.hpp"
 #include "fmx_device.hpp"
 #include "fmx_internal.hpp"
 
@@ -151,7 +152,8 @@ __global__ __launch_bounds__(kRowThreads) void k_extract_rows(const float4* __re
   TSTAMP();
 
   if constexpr (PAR) {
-    // ================= sector-parallel selection (pps <= 512, S <= 16) ==============
+    // ================= sector-parallel selection (extract_plan: S <= 16 and at most
+    // kSortCapacity candidates in any sector) ==============
     // Sectors interact only through suppression spilling k-1 columns over a sector
     // boundary (parity hazard 5).  Every sector is run speculatively at once (wave s
     // = sector s) as if nothing spilled in; then, in sector order, sector s is re-run
@@ -186,14 +188,16 @@ __global__ __launch_bounds__(kRowThreads) void k_extract_rows(const float4* __re
     __syncthreads();
     TSTAMP();
     // P2: wave s bitonic-sorts sector s's keys in registers (8 per lane, blocked:
-    // element e = lane * 8 + u), pads with ~0
+    // element e = lane * 8 + u), pads with ~0.  n <= kSortCapacity: extract_plan sends
+    // every shape whose longest sector could hold more to the sequential kernel.
+    static_assert(kSortCapacity == 8 * kWave, "the register sort holds 8 keys per lane");
     if (w < S) {
       const int b = sec_b(w), n = s_cntS[w];
       uint64_t v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) v[u] = lane * 8 + u < n ? keys[b + lane * 8 + u] : ~0ull;
 #pragma unroll
-      for (int kk = 2; kk <= 512; kk <<= 1) {
+      for (int kk = 2; kk <= kSortCapacity; kk <<= 1) {
 #pragma unroll
         for (int j = kk >> 1; j > 0; j >>= 1) {
           if (j >= 8) {
@@ -1034,7 +1038,6 @@ __device__ int fit_one(const float4* __restrict__ scan, const uint32_t* __restri
 //   fit:     one lane per selected point, the reference's neighbour push order.
 // The row's found-normal count is stored directly (one block per row).
 constexpr int kNrmThreads = 1024;
-constexpr int kNrmMaxC = 2048;
 
 template <int KC>
 __global__ __launch_bounds__(kNrmThreads) void k_normals(const float4* __restrict__ scan,
@@ -1444,12 +1447,12 @@ static ExArgs extract_setup(fmx_ctx* c, int R, int C) {
   c->rows = R;
   c->cols = C;
   if (!c->lds_attr_set) {
-    const int lmax = 4096 * (16 + 4 + 4 + 4 + 4);
     const void* kern[4] = {reinterpret_cast<const void*>(k_extract_rows<5, false>),
                            reinterpret_cast<const void*>(k_extract_rows<0, false>),
                            reinterpret_cast<const void*>(k_extract_rows<5, true>),
                            reinterpret_cast<const void*>(k_extract_rows<0, true>)};
-    for (const void* kf : kern) FMX_HIP(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, lmax));
+    for (const void* kf : kern)
+      FMX_HIP(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRowLdsMax));
     c->lds_attr_set = true;
   }
   return a;
@@ -1460,26 +1463,20 @@ static void launch_rows(fmx_ctx* c, const float4* d_scan, ExArgs a, int r0, int 
   if (r1 <= r0) return;
   const int R = a.R, C = a.C;
   const size_t N = (size_t)R * C;
-  const size_t lds = (size_t)C * (16 + 4 + 4 + 4 + 4);
-  // sector-parallel selection when every sector sorts in one wave's registers (<= 512
-  // columns), there is a wave per sector, sectors are longer than the suppression
-  // reach, and the kept lists fit the dead point area of LDS
-  const int pps = C / a.S;
-  const size_t nwd = (size_t)(C + 63) / 64 + 1;
-  const bool par = pps <= 512 && a.S <= 16 && pps >= 2 * a.k &&
-                   8 * (size_t)C + 8 * nwd + 2 * 4 * (size_t)a.S * (a.P + 1) <= 16 * (size_t)C;
+  const ExtractPlan plan = extract_plan(R, C, a.k, a.S, a.P);
+  const size_t lds = plan.lds_rows;
   a.row0 = r0;
   const dim3 grid(r1 - r0);
   ProfScope ps(c->prof, PROF_EXTRACT_ROWS, (16.0 * N + N) * (r1 - r0) / R, st);
-  if (par) {
-    if (a.k == 5)
+  if (plan.sector_parallel) {
+    if (plan.kc5)
       hipLaunchKernelGGL((k_extract_rows<5, true>), grid, dim3(kRowThreads), lds, st, d_scan, a, c->planar_mask.p,
                          c->sel_slots.p, c->pt_slots.p, c->row_counts.p);
     else
       hipLaunchKernelGGL((k_extract_rows<0, true>), grid, dim3(kRowThreads), lds, st, d_scan, a, c->planar_mask.p,
                          c->sel_slots.p, c->pt_slots.p, c->row_counts.p);
   } else {
-    if (a.k == 5)
+    if (plan.kc5)
       hipLaunchKernelGGL((k_extract_rows<5, false>), grid, dim3(kRowThreads), lds, st, d_scan, a, c->planar_mask.p,
                          c->sel_slots.p, c->pt_slots.p, c->row_counts.p);
     else
@@ -1497,12 +1494,10 @@ ExLaunch extract_launch(fmx_ctx* c, const float4* d_scan, int R, int C, hipStrea
   const size_t N = (size_t)R * C;
   const int nslots = R * a.cap_pl;
   const int nblk = (C + 63) / 64;
-  // k_normals: one workgroup per line, rows r-1..r+1 in LDS (160 KB per CU, minus
-  // the kernel's few static bytes)
-  const size_t lds_n = (size_t)3 * (C + (C >> 6) + 1) * 16 + (size_t)4 * nblk * 16 + (size_t)a.cap_pl * 20 +
-                       (size_t)a.cap_pl * nblk * 4;
-  constexpr size_t kNrmLdsMax = 160 * 1024 - 256;
-  if (C <= kNrmMaxC && lds_n <= kNrmLdsMax) {
+  // k_normals: one workgroup per line, rows r-1..r+1 in LDS, when the line fits
+  const ExtractPlan plan = extract_plan(R, C, a.k, a.S, a.P);
+  const size_t lds_n = plan.lds_normals;
+  if (plan.fused_normals) {
     if (!c->nrm_attr_set) {
       FMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_normals<5>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNrmLdsMax));
@@ -1511,7 +1506,7 @@ ExLaunch extract_launch(fmx_ctx* c, const float4* d_scan, int R, int C, hipStrea
       c->nrm_attr_set = true;
     }
     ProfScope ps(c->prof, PROF_FIT, 48.0 * N + 2.0 * N + 16.0 * nslots, st);
-    if (a.k == 5)
+    if (plan.kc5)
       hipLaunchKernelGGL(k_normals<5>, dim3(R, 2), dim3(kNrmThreads), lds_n, st, d_scan, c->planar_mask.p, c->sel_slots.p,
                          c->row_counts.p, a, c->nrm_slots.p, c->row_ok.p);
     else
