@@ -1436,7 +1436,7 @@ static ExArgs extract_setup(fmx_ctx* c, int R, int C) {
   a.radius2 = E.radius * E.radius;
   a.min_points = (int)E.min_points;
   const size_t N = (size_t)R * C;
-  c->planar_mask.ensure(N);
+  c->q.planar_mask.ensure(N);
   c->sel_slots.ensure((size_t)R * a.cap_pl);
   c->pt_slots.ensure((size_t)R * a.cap_pt);
   c->row_counts.ensure(2 * (size_t)R);
@@ -1470,17 +1470,17 @@ static void launch_rows(fmx_ctx* c, const float4* d_scan, ExArgs a, int r0, int 
   ProfScope ps(c->prof, PROF_EXTRACT_ROWS, (16.0 * N + N) * (r1 - r0) / R, st);
   if (plan.sector_parallel) {
     if (plan.kc5)
-      hipLaunchKernelGGL((k_extract_rows<5, true>), grid, dim3(kRowThreads), lds, st, d_scan, a, c->planar_mask.p,
+      hipLaunchKernelGGL((k_extract_rows<5, true>), grid, dim3(kRowThreads), lds, st, d_scan, a, c->q.planar_mask.p,
                          c->sel_slots.p, c->pt_slots.p, c->row_counts.p);
     else
-      hipLaunchKernelGGL((k_extract_rows<0, true>), grid, dim3(kRowThreads), lds, st, d_scan, a, c->planar_mask.p,
+      hipLaunchKernelGGL((k_extract_rows<0, true>), grid, dim3(kRowThreads), lds, st, d_scan, a, c->q.planar_mask.p,
                          c->sel_slots.p, c->pt_slots.p, c->row_counts.p);
   } else {
     if (plan.kc5)
-      hipLaunchKernelGGL((k_extract_rows<5, false>), grid, dim3(kRowThreads), lds, st, d_scan, a, c->planar_mask.p,
+      hipLaunchKernelGGL((k_extract_rows<5, false>), grid, dim3(kRowThreads), lds, st, d_scan, a, c->q.planar_mask.p,
                          c->sel_slots.p, c->pt_slots.p, c->row_counts.p);
     else
-      hipLaunchKernelGGL((k_extract_rows<0, false>), grid, dim3(kRowThreads), lds, st, d_scan, a, c->planar_mask.p,
+      hipLaunchKernelGGL((k_extract_rows<0, false>), grid, dim3(kRowThreads), lds, st, d_scan, a, c->q.planar_mask.p,
                          c->sel_slots.p, c->pt_slots.p, c->row_counts.p);
   }
   FMX_HIP(hipGetLastError());
@@ -1507,10 +1507,10 @@ ExLaunch extract_launch(fmx_ctx* c, const float4* d_scan, int R, int C, hipStrea
     }
     ProfScope ps(c->prof, PROF_FIT, 48.0 * N + 2.0 * N + 16.0 * nslots, st);
     if (plan.kc5)
-      hipLaunchKernelGGL(k_normals<5>, dim3(R, 2), dim3(kNrmThreads), lds_n, st, d_scan, c->planar_mask.p, c->sel_slots.p,
+      hipLaunchKernelGGL(k_normals<5>, dim3(R, 2), dim3(kNrmThreads), lds_n, st, d_scan, c->q.planar_mask.p, c->sel_slots.p,
                          c->row_counts.p, a, c->nrm_slots.p, c->row_ok.p);
     else
-      hipLaunchKernelGGL(k_normals<0>, dim3(R, 2), dim3(kNrmThreads), lds_n, st, d_scan, c->planar_mask.p, c->sel_slots.p,
+      hipLaunchKernelGGL(k_normals<0>, dim3(R, 2), dim3(kNrmThreads), lds_n, st, d_scan, c->q.planar_mask.p, c->sel_slots.p,
                          c->row_counts.p, a, c->nrm_slots.p, c->row_ok.p);
     FMX_HIP(hipGetLastError());
   } else {
@@ -1519,9 +1519,9 @@ ExLaunch extract_launch(fmx_ctx* c, const float4* d_scan, int R, int C, hipStrea
     c->blk_hi.ensure((size_t)R * nblk);
     {
       ProfScope ps(c->prof, PROF_CLOSEST, 16.0 * N + N + 8.0 * nslots, st);
-      hipLaunchKernelGGL(k_row_blocks, dim3((R * nblk + 3) / 4), dim3(256), 0, st, d_scan, c->planar_mask.p, R, C,
+      hipLaunchKernelGGL(k_row_blocks, dim3((R * nblk + 3) / 4), dim3(256), 0, st, d_scan, c->q.planar_mask.p, R, C,
                          c->blk_lo.p, c->blk_hi.p);
-      hipLaunchKernelGGL(k_closest, dim3((nslots + 3) / 4), dim3(256), 0, st, d_scan, c->planar_mask.p,
+      hipLaunchKernelGGL(k_closest, dim3((nslots + 3) / 4), dim3(256), 0, st, d_scan, c->q.planar_mask.p,
                          c->sel_slots.p, c->row_counts.p, R, C, a.cap_pl, c->blk_lo.p, c->blk_hi.p, c->closest.p);
     }
     {
@@ -1542,16 +1542,16 @@ ExLaunch extract_launch(fmx_ctx* c, const float4* d_scan, int R, int C, hipStrea
   // k_row_scan), and so is any independent work of the caller (register_scan: the
   // map build on the side stream)
   const size_t max_pl = (size_t)R * a.cap_pl, max_pt = (size_t)R * a.cap_pt;
-  c->q_pl_pos.ensure(max_pl + 1);
-  c->q_pl_nrm.ensure(max_pl + 1);
-  c->q_pl_idx.ensure(max_pl + 1);
-  c->q_pt_pos.ensure(max_pt + 1);
-  c->q_pt_idx.ensure(max_pt + 1);
+  c->q.pl_pos.ensure(max_pl + 1);
+  c->q.pl_nrm.ensure(max_pl + 1);
+  c->q.pl_idx.ensure(max_pl + 1);
+  c->q.pt_pos.ensure(max_pt + 1);
+  c->q.pt_idx.ensure(max_pt + 1);
   {
     ProfScope ps(c->prof, PROF_COMPACT, 32.0 * c->n_qpl + 16.0 * c->n_qpt, st);  // byte model: last totals
     hipLaunchKernelGGL(k_write_features, dim3(R), dim3(256), 0, st, d_scan, a, c->row_counts.p, c->row_off.p,
-                       c->sel_slots.p, c->pt_slots.p, c->nrm_slots.p, c->q_pl_pos.p, c->q_pl_nrm.p,
-                       c->q_pl_idx.p, c->q_pt_pos.p, c->q_pt_idx.p);
+                       c->sel_slots.p, c->pt_slots.p, c->nrm_slots.p, c->q.pl_pos.p, c->q.pl_nrm.p,
+                       c->q.pl_idx.p, c->q.pt_pos.p, c->q.pt_idx.p);
   }
   FMX_HIP(hipGetLastError());
   ExLaunch L;

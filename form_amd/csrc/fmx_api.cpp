@@ -43,17 +43,17 @@ void run_match(fmx_ctx* c, const double* pose_j34, double max_dist, double min_d
                bool defer_scatter) {
   HostScope hs(16);
   ++c->corr_gen;
-  c->match_group = match_group_for((uint64_t)c->n_qpl + c->n_qpt, c->K);
-  if (c->match_group != 8) gl::run_match(c, pose_j34, max_dist, min_dist_map, sorted, defer_scatter);
+  c->m.match_group = match_group_for((uint64_t)c->n_qpl + c->n_qpt, c->K);
+  if (c->m.match_group != 8) gl::run_match(c, pose_j34, max_dist, min_dist_map, sorted, defer_scatter);
   else g8::run_match(c, pose_j34, max_dist, min_dist_map, sorted, defer_scatter);
 }
 void run_pair_scatter(fmx_ctx* c) {
   HostScope hs(17);
-  if (c->match_group != 8) gl::run_pair_scatter(c);
+  if (c->m.match_group != 8) gl::run_pair_scatter(c);
   else g8::run_pair_scatter(c);
 }
 void run_insert(fmx_ctx* c, uint64_t scan, uint32_t* n_inserted) {
-  if (c->match_group != 8) gl::run_insert(c, scan, n_inserted);
+  if (c->m.match_group != 8) gl::run_insert(c, scan, n_inserted);
   else g8::run_insert(c, scan, n_inserted);
 }
 void run_match_linearize(fmx_ctx* c, const double* pose_j34, double max_dist, double sigma, double* dst,
@@ -63,7 +63,7 @@ void run_match_linearize(fmx_ctx* c, const double* pose_j34, double max_dist, do
   gl::run_match_linearize(c, pose_j34, max_dist, sigma, dst, flag, seq);
 }
 void match_counts_fetch(fmx_ctx* c, bool wait) {
-  if (c->match_group != 8) gl::match_counts_fetch(c, wait);
+  if (c->m.match_group != 8) gl::match_counts_fetch(c, wait);
   else g8::match_counts_fetch(c, wait);
 }
 
@@ -102,7 +102,7 @@ ProfScope::~ProfScope() {
   e.queries = queries;
   pr.pending.push_back(e);
 }
-// every stream of the context: main, side (map build), side2 (pipelined extraction)
+// every stream of the context: main, side (map build), side2 (pipelined extraction), lin
 static void sync_all(fmx_ctx* c) {
   FMX_HIP(hipStreamSynchronize(c->stream));
   if (c->side) FMX_HIP(hipStreamSynchronize(c->side));
@@ -214,9 +214,9 @@ void settle_match(fmx_ctx* c) {
 void drop_match(fmx_ctx* c) {
   if (!c->lazy.pending) return;
   c->lazy.pending = false;
-  c->have_match = false;
-  c->have_qo = false;
-  c->have_corr = false;
+  c->m.have_match = false;
+  c->m.have_qo = false;
+  c->m.have_corr = false;
 }
 
 // SETTLE: run a deferred fmx_match first — every entry point but fmx_match itself,
@@ -268,12 +268,8 @@ void compact_pool(fmx_ctx* c, int t) {
     o += r.second;
   }
   FMX_HIP(hipStreamSynchronize(c->stream));
-  pool.pos.release();
-  pool.pos = npos;
-  if (t == 0) {
-    pool.nrm.release();
-    pool.nrm = nnrm;
-  }
+  pool.pos = std::move(npos);  // frees the old pool
+  if (t == 0) pool.nrm = std::move(nnrm);
   pool.used = o;
 }
 
@@ -320,28 +316,33 @@ void pool_add_device(fmx_ctx* c, int t, uint64_t scan, const float* pos4, const 
   pool.used += n;
 }
 
-void set_queries_device(fmx_ctx* c, uint64_t scan, const float* plp, const float* pln, uint32_t npl, const float* ptp,
-                        uint32_t npt) {
-  c->q_pl_pos.ensure(npl + 1);
-  c->q_pl_nrm.ensure(npl + 1);
-  c->q_pl_idx.ensure(npl + 1);
-  c->q_pt_pos.ensure(npt + 1);
-  c->q_pt_idx.ensure(npt + 1);
-  if (npl) {
-    FMX_HIP(hipMemcpyAsync(c->q_pl_pos.p, plp, npl * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    FMX_HIP(hipMemcpyAsync(c->q_pl_nrm.p, pln, npl * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-  }
-  if (npt) FMX_HIP(hipMemcpyAsync(c->q_pt_pos.p, ptp, npt * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-  FMX_HIP(hipMemsetAsync(c->q_pl_idx.p, 0xFF, (npl + 1) * sizeof(uint32_t), c->stream));
-  FMX_HIP(hipMemsetAsync(c->q_pt_idx.p, 0xFF, (npt + 1) * sizeof(uint32_t), c->stream));
-  c->n_qpl = npl;
-  c->n_qpt = npt;
-  c->n_sel = npl;
+// The current query set now holds scan `scan`'s features: nothing matched so far applies.
+void query_set_replaced(fmx_ctx* c, uint64_t scan) {
   c->q_scan = scan;
   c->have_queries = true;
   ++c->warm_gen;  // a new query set: no warm start from an earlier match
-  c->have_match = false;
-  c->have_qo = false;
+  c->m.have_match = false;
+  c->m.have_qo = false;
+}
+
+void set_queries_device(fmx_ctx* c, uint64_t scan, const float* plp, const float* pln, uint32_t npl, const float* ptp,
+                        uint32_t npt) {
+  c->q.pl_pos.ensure(npl + 1);
+  c->q.pl_nrm.ensure(npl + 1);
+  c->q.pl_idx.ensure(npl + 1);
+  c->q.pt_pos.ensure(npt + 1);
+  c->q.pt_idx.ensure(npt + 1);
+  if (npl) {
+    FMX_HIP(hipMemcpyAsync(c->q.pl_pos.p, plp, npl * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    FMX_HIP(hipMemcpyAsync(c->q.pl_nrm.p, pln, npl * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (npt) FMX_HIP(hipMemcpyAsync(c->q.pt_pos.p, ptp, npt * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  FMX_HIP(hipMemsetAsync(c->q.pl_idx.p, 0xFF, (npl + 1) * sizeof(uint32_t), c->stream));
+  FMX_HIP(hipMemsetAsync(c->q.pt_idx.p, 0xFF, (npt + 1) * sizeof(uint32_t), c->stream));
+  c->n_qpl = npl;
+  c->n_qpt = npt;
+  c->n_sel = npl;
+  query_set_replaced(c, scan);
 }
 
 void set_queries(fmx_ctx* c, uint64_t scan, const float* pl, uint32_t npl, const float* pt, uint32_t npt) {
@@ -351,24 +352,20 @@ void set_queries(fmx_ctx* c, uint64_t scan, const float* pl, uint32_t npl, const
     b[i] = make_float4(pl[6 * i + 3], pl[6 * i + 4], pl[6 * i + 5], 0.f);
   }
   for (uint32_t i = 0; i < npt; ++i) d[i] = make_float4(pt[3 * i], pt[3 * i + 1], pt[3 * i + 2], 0.f);
-  c->q_pl_pos.ensure(npl + 1);
-  c->q_pl_nrm.ensure(npl + 1);
-  c->q_pl_idx.ensure(npl + 1);
-  c->q_pt_pos.ensure(npt + 1);
-  c->q_pt_idx.ensure(npt + 1);
-  FMX_HIP(hipMemcpy(c->q_pl_pos.p, a.data(), (npl + 1) * sizeof(float4), hipMemcpyHostToDevice));
-  FMX_HIP(hipMemcpy(c->q_pl_nrm.p, b.data(), (npl + 1) * sizeof(float4), hipMemcpyHostToDevice));
-  FMX_HIP(hipMemcpy(c->q_pt_pos.p, d.data(), (npt + 1) * sizeof(float4), hipMemcpyHostToDevice));
-  FMX_HIP(hipMemsetAsync(c->q_pl_idx.p, 0xFF, (npl + 1) * sizeof(uint32_t), c->stream));
-  FMX_HIP(hipMemsetAsync(c->q_pt_idx.p, 0xFF, (npt + 1) * sizeof(uint32_t), c->stream));
+  c->q.pl_pos.ensure(npl + 1);
+  c->q.pl_nrm.ensure(npl + 1);
+  c->q.pl_idx.ensure(npl + 1);
+  c->q.pt_pos.ensure(npt + 1);
+  c->q.pt_idx.ensure(npt + 1);
+  FMX_HIP(hipMemcpy(c->q.pl_pos.p, a.data(), (npl + 1) * sizeof(float4), hipMemcpyHostToDevice));
+  FMX_HIP(hipMemcpy(c->q.pl_nrm.p, b.data(), (npl + 1) * sizeof(float4), hipMemcpyHostToDevice));
+  FMX_HIP(hipMemcpy(c->q.pt_pos.p, d.data(), (npt + 1) * sizeof(float4), hipMemcpyHostToDevice));
+  FMX_HIP(hipMemsetAsync(c->q.pl_idx.p, 0xFF, (npl + 1) * sizeof(uint32_t), c->stream));
+  FMX_HIP(hipMemsetAsync(c->q.pt_idx.p, 0xFF, (npt + 1) * sizeof(uint32_t), c->stream));
   c->n_qpl = npl;
   c->n_qpt = npt;
   c->n_sel = npl;
-  c->q_scan = scan;
-  c->have_queries = true;
-  ++c->warm_gen;  // a new query set: no warm start from an earlier match
-  c->have_match = false;
-  c->have_qo = false;
+  query_set_replaced(c, scan);
 }
 
 // ---- host-resident scans (stage.hpp)
@@ -400,14 +397,11 @@ void pinned_ensure(fmx_ctx* c, size_t bytes) {
   c->stager.retire(&c->st_pf[0]);
   c->stager.retire(&c->st_pf[1]);
   sync_all(c);
-  uint8_t** bufs[3] = {&c->pin_seq, &c->pin_pf[0], &c->pin_pf[1]};
-  for (uint8_t** b : bufs) {
-    if (*b) (void)hipHostFree(*b);
-    *b = nullptr;
-  }
+  PinBuf<uint8_t>* bufs[3] = {&c->pin_seq, &c->pin_pf[0], &c->pin_pf[1]};
+  for (auto* b : bufs) b->release();
   c->pin_cap = 0;
   c->ann_ptr = nullptr;  // a staged announcement lived in the old buffers
-  for (uint8_t** b : bufs) FMX_HIP(hipHostMalloc(reinterpret_cast<void**>(b), bytes, hipHostMallocDefault));
+  for (auto* b : bufs) b->alloc(bytes);
   c->pin_cap = bytes;
 }
 // Start the staging copy of `bytes` host bytes into pinned `dst` (helpers, if any).
@@ -454,7 +448,7 @@ const float4* stage_host_scan(fmx_ctx* c, const float* xyzw, size_t n) {
   // pin_seq's previous DMA was on the context stream ahead of an extraction whose totals
   // the host waited for: it has completed
   StageReq& r = c->st_seq;
-  stage_submit(c, r, xyzw, c->pin_seq, bytes);
+  stage_submit(c, r, xyzw, c->pin_seq.p, bytes);
   c->scan3.ensure(3 * n);
   uint8_t* dev = reinterpret_cast<uint8_t*>(c->scan3.p);
   const uint32_t step = std::max<uint32_t>(1, (r.nchunks + stage_dmas() - 1) / stage_dmas());
@@ -464,7 +458,7 @@ const float4* stage_host_scan(fmx_ctx* c, const float* xyzw, size_t n) {
     while (ready < r.nchunks && r.chunk_done(ready)) ++ready;
     if (ready - issued >= step || ready == r.nchunks) {
       const size_t a = (size_t)issued * r.chunk / 16 * 12, b = std::min(bytes, (size_t)ready * r.chunk) / 16 * 12;
-      FMX_HIP(hipMemcpyAsync(dev + a, c->pin_seq + a, b - a, hipMemcpyHostToDevice, c->stream));
+      FMX_HIP(hipMemcpyAsync(dev + a, c->pin_seq.p + a, b - a, hipMemcpyHostToDevice, c->stream));
       issued = ready;
       continue;
     }
@@ -500,20 +494,12 @@ void do_extract(fmx_ctx* c, const float* xyzw, size_t n, uint64_t scan, int on_d
     d = c->dsk.out.p;
   }
   run_extract(c, d, (int)R, (int)C, out, while_waiting);
-  c->q_scan = scan;
-  c->have_queries = true;
-  ++c->warm_gen;  // a new query set: no warm start from an earlier match
-  c->have_match = false;
-  c->have_qo = false;
+  query_set_replaced(c, scan);
 }
 
 // ---- pipelined extraction (fmx_next_scan)
-// Exchange the current query set (+ planar mask) with the second one.
-void swap_query_set(fmx_ctx* c) {
-  using std::swap;
-  swap(c->q_pl_pos, c->nq_pl_pos); swap(c->q_pl_nrm, c->nq_pl_nrm); swap(c->q_pt_pos, c->nq_pt_pos);
-  swap(c->q_pl_idx, c->nq_pl_idx); swap(c->q_pt_idx, c->nq_pt_idx); swap(c->planar_mask, c->n_planar_mask);
-}
+// Exchange the current query set with the second one.
+void swap_query_set(fmx_ctx* c) { std::swap(c->q, c->nq); }
 // Discard a queued extraction of an announced scan (its buffers are then free again).
 void pf_drop(fmx_ctx* c) {
   if (c->pf_launched) {
@@ -563,7 +549,7 @@ void pf_launch(fmx_ctx* c, bool force = true, const double* dsk_xi = nullptr, in
       FMX_HIP(hipMemcpyAsync(c->pf_scan.p, c->ann_ptr, c->ann_n * sizeof(float4), hipMemcpyHostToDevice, xs));
     } else {  // staged as packed x, y, z
       c->pf_scan3.ensure(3 * c->ann_n);
-      FMX_HIP(hipMemcpyAsync(c->pf_scan3.p, c->pin_pf[c->ann_slot], c->ann_n * 12, hipMemcpyHostToDevice, xs));
+      FMX_HIP(hipMemcpyAsync(c->pf_scan3.p, c->pin_pf[c->ann_slot].p, c->ann_n * 12, hipMemcpyHostToDevice, xs));
       unpack_xyz(c, c->pf_scan3.p, c->pf_scan.p, c->ann_n, xs);
     }
     d = c->pf_scan.p;
@@ -613,11 +599,7 @@ bool pf_take(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, uint64_t scan,
   if (while_waiting && !flag_reached(*c->pf_L.flag, c->pf_L.seq)) (*while_waiting)();
   extract_collect(c, c->pf_L, out);
   ++c->pf_used;
-  c->q_scan = scan;
-  c->have_queries = true;
-  ++c->warm_gen;  // a new query set: no warm start from an earlier match
-  c->have_match = false;
-  c->have_qo = false;
+  query_set_replaced(c, scan);
   return true;
 }
 
@@ -870,26 +852,10 @@ void set_lin(WinGraph& g, B begin, E end) {
   g.lin_end = end;
 }
 
-// Exchange the context's match results with the speculative set (fmx::MatchSet).
+// Exchange the current match set with the speculative one.
 void swap_match_set(fmx_ctx* c) {
-  MatchSet& S = c->spec;
-  using std::swap;
   ++c->corr_gen;
-  swap(c->m_pair, S.m_pair); swap(c->m_d2, S.m_d2); swap(c->m_pi, S.m_pi); swap(c->m_ni, S.m_ni);
-  swap(c->m_ins, S.m_ins); swap(c->hist, S.hist); swap(c->hist_off, S.hist_off); swap(c->thist, S.thist);
-  swap(c->thist_par, S.thist_par);
-  swap(c->c_pl, S.c_pl); swap(c->c_pt, S.c_pt); swap(c->pair_counts, S.pair_counts);
-  swap(c->chunk_range, S.chunk_range); swap(c->chunks, S.chunks); swap(c->n_chunks, S.n_chunks);
-  swap(c->pair_base, S.pair_base); swap(c->work, S.work); swap(c->mcnt, S.mcnt); swap(c->mticket, S.mticket);
-  swap(c->ins_blk, S.ins_blk); swap(c->ins_off, S.ins_off); swap(c->h_counts, S.h_counts); swap(c->h_work, S.h_work);
-  swap(c->have_match, S.have_match); swap(c->have_corr, S.have_corr); swap(c->scatter_pending, S.scatter_pending);
-  swap(c->counts_pending, S.counts_pending); swap(c->have_qo, S.have_qo); swap(c->ld_pl, S.ld_pl);
-  swap(c->ld_pt, S.ld_pt); swap(c->max_chunks, S.max_chunks); swap(c->work_blocks, S.work_blocks);
-  swap(c->work_copied, S.work_copied);
-  swap(c->match_nb_pl, S.match_nb_pl); swap(c->match_nb, S.match_nb); swap(c->n_qo, S.n_qo);
-  swap(c->match_group, S.match_group); swap(c->ps, S.ps); swap(c->rows_pl, S.rows_pl); swap(c->rows_pt, S.rows_pt);
-  swap(c->cnt_pl, S.cnt_pl); swap(c->cnt_pt, S.cnt_pt); swap(c->last_probes, S.last_probes);
-  swap(c->last_cands, S.last_cands); swap(c->ins_tot, S.ins_tot); swap(c->cert_tot, S.cert_tot);
+  std::swap(c->m, c->spec);
 }
 
 // Speculative match (smoothing-mode ICP): when an LM trial is probably the LM's last
@@ -1049,7 +1015,7 @@ void smooth_register(fmx_ctx* c, fmx_ctx::Est& e, uint64_t j, uint32_t nfeat, co
           mref[K] = x[slot.at(j)];
           for (int k = 0; k <= K; ++k) std::memcpy(&table[12 * k], mref[k].m, 12 * sizeof(double));
           momv.resize((size_t)std::max(K, 1) * kMomPairD);
-          FMX_TRACE_("scan %llu it %u: moments launch K %d chunks %u\n", (unsigned long long)j, it, K, c->max_chunks);
+          FMX_TRACE_("scan %llu it %u: moments launch K %d chunks %u\n", (unsigned long long)j, it, K, c->m.max_chunks);
           win_moments_current(c, table.data(), nullptr);  // launch only; win_finish in lin_end
           FMX_TRACE_("  launched\n");
           launched = true;
@@ -1070,7 +1036,7 @@ void smooth_register(fmx_ctx* c, fmx_ctx::Est& e, uint64_t j, uint32_t nfeat, co
           FMX_TRACE_("  moments in\n");
           match_counts_fetch(c, false);  // the match finished before the moments
           for (int k = 0; k < K; ++k)  // pairs without rows are never written by the kernel
-            if (c->cnt_pl[k] + c->cnt_pt[k] == 0)
+            if (c->m.cnt_pl[k] + c->m.cnt_pt[k] == 0)
               std::fill(&momv[(size_t)k * kMomPairD], &momv[(size_t)(k + 1) * kMomPairD], 0.0);
           mp.resize(K);
           mri.resize(K);
@@ -1108,7 +1074,7 @@ void smooth_register(fmx_ctx* c, fmx_ctx::Est& e, uint64_t j, uint32_t nfeat, co
         win_finish(c, G);
         match_counts_fetch(c, false);  // the match finished before the linearization
         for (int k = 0; k < K; ++k)
-          if (c->cnt_pl[k] + c->cnt_pt[k] == 0) std::fill(G + (size_t)k * kPairG, G + (size_t)(k + 1) * kPairG, 0.0);
+          if (c->m.cnt_pl[k] + c->m.cnt_pt[k] == 0) std::fill(G + (size_t)k * kPairG, G + (size_t)(k + 1) * kPairG, 0.0);
       };
       set_lin(g, lin_begin, lin_end);
     }
@@ -1132,7 +1098,7 @@ void smooth_register(fmx_ctx* c, fmx_ctx::Est& e, uint64_t j, uint32_t nfeat, co
   record_cons(c, e, j);
   if (mom_full) {
     for (uint32_t k = 0; k < c->K; ++k)
-      if (c->cnt_pl[k] + c->cnt_pt[k] > 0) {
+      if (c->m.cnt_pl[k] + c->m.cnt_pt[k] > 0) {
         fmx_ctx::Est::Mom& m = e.moms[{j, c->map_scans[k]}];
         m.ref_i = mref[k];
         m.ref_j = mref[c->K];
@@ -1365,9 +1331,9 @@ void record_cons(fmx_ctx* c, fmx_ctx::Est& e, uint64_t j) {
   auto& cj = e.cons[j];
   e.last_mpl = e.last_mpt = 0;
   for (uint32_t k = 0; k < c->K; ++k) {
-    cj[c->map_scans[k]] = {c->cnt_pl[k], c->cnt_pt[k]};
-    e.last_mpl += c->cnt_pl[k];
-    e.last_mpt += c->cnt_pt[k];
+    cj[c->map_scans[k]] = {c->m.cnt_pl[k], c->m.cnt_pt[k]};
+    e.last_mpl += c->m.cnt_pl[k];
+    e.last_mpt += c->m.cnt_pt[k];
   }
   e.last_map_pl = c->map.n[0];
   e.last_map_pt = c->map.n[1];
@@ -1720,97 +1686,24 @@ fmx_status fmx_create(const fmx_params* p, int device, fmx_ctx** out) {
   return FMX_OK;
 }
 
+// Nothing may still run on the device, and no helper thread may still copy, when the
+// members' destructors free the buffers that work reads and writes: so the waits and
+// stager.stop() come first, before any member is destroyed.  Errors are ignored (a
+// half-built context of a failed fmx_create comes here too).  The caller has made the
+// context's device current.
+fmx_ctx::~fmx_ctx() {
+  for (hipStream_t s : {stream, side, side2, lin})
+    if (s) (void)hipStreamSynchronize(s);
+  stager.stop();
+  delete est;
+  comm_destroy(this);
+  for (hipStream_t s : {stream, side, side2, lin})
+    if (s) (void)hipStreamDestroy(s);
+}
+
 void fmx_destroy(fmx_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->side) (void)hipStreamSynchronize(c->side);
-  if (c->side2) (void)hipStreamSynchronize(c->side2);
-  for (auto& e : c->prof.free_events) (void)hipEventDestroy(e);
-  for (auto& pe : c->prof.pending) {
-    (void)hipEventDestroy(pe.a);
-    (void)hipEventDestroy(pe.b);
-  }
-  c->prof.wring.release();
-  delete c->est;
-  comm_destroy(c);
-  c->d_sum.release();
-  c->h_hold.release();
-  // DBuf/HBuf members do not free in their destructors: release explicitly.
-  c->scan.release(); c->planar_mask.release(); c->sel_slots.release(); c->pt_slots.release();
-  c->row_counts.release(); c->row_ok.release(); c->row_off.release(); c->closest.release();
-  c->nrm_slots.release(); c->scan_scratch.release(); c->dev_u32.release(); c->h_u32.release();
-  c->q_pl_pos.release(); c->q_pl_nrm.release(); c->q_pt_pos.release(); c->q_pl_idx.release(); c->q_pt_idx.release();
-  c->nq_pl_pos.release(); c->nq_pl_nrm.release(); c->nq_pt_pos.release(); c->nq_pl_idx.release(); c->nq_pt_idx.release();
-  c->n_planar_mask.release(); c->h_pf.release();
-  c->stager.stop();  // no helper touches the staging buffers after this
-  for (uint8_t* b : {c->pin_seq, c->pin_pf[0], c->pin_pf[1]})
-    if (b) (void)hipHostFree(b);
-  c->pf_scan.release();
-  c->scan3.release();
-  c->pf_scan3.release();
-  c->dsk.frac.release();
-  c->dsk.out.release();
-  c->dsk.pf_out.release();
-  c->dsk.io_in.release();
-  c->dsk.io_out.release();
-  c->org.ring_to_row.release();
-  c->org.mid.release();
-  c->org.keys.release();
-  c->org.cnt.release();
-  c->org.h_cnt.release();
-  c->org.out[0].release();
-  c->org.out[1].release();
-  c->org.index.release();
-  c->org.frac.release();
-  c->org.in_xyzw.release();
-  c->org.in_ring.release();
-  c->org.in_frac.release();
-  for (auto& B : c->scanbuf)
-    if (B.p) (void)hipHostFree(B.p);
-  for (int t = 0; t < 2; ++t) {
-    c->pool[t].pos.release(); c->pool[t].nrm.release();
-    c->segs[t].release(); c->h_segs[t].release();
-  }
-  {
-    auto& M = c->map;
-    M.table.release(); M.ccnt.release(); M.state.release(); M.rinfo.release(); M.claim.release(); M.dense.release();
-    M.pos.release(); M.nrm.release();
-  }
-  c->h_mapposes.release(); c->map_blob.release(); c->h_mapinfo.release();
-  c->blk_lo.release(); c->blk_hi.release(); c->h_work.release();
-  c->work.release(); c->pair_base.release();
-  c->m_pair.release(); c->m_d2.release(); c->m_pi.release(); c->m_ni.release(); c->m_ins.release();
-  c->m_rec.release(); c->m_cell.release();
-  c->hist.release(); c->hist_off.release(); c->thist.release(); c->c_pl.release(); c->c_pt.release(); c->pair_counts.release();
-  c->chunk_range.release(); c->chunks.release(); c->n_chunks.release();
-  c->bpart.release(); c->ticket.release(); c->h_poses.release(); c->h_G.release(); c->h_i32.release();
-  c->h_corr.release(); c->h_meta.release(); c->h_counts.release(); c->h_flag.release();
-  c->mcnt.release(); c->mticket.release(); c->ins_blk.release(); c->ins_off.release();
-  c->fz_work.release(); c->fz_h_work.release(); c->fz_tickets.release(); c->mprof.release();
-  c->cert_b2.release();
-  {
-    auto& S = c->spec;
-    S.m_pair.release(); S.m_d2.release(); S.m_pi.release(); S.m_ni.release(); S.m_ins.release();
-    S.hist.release(); S.hist_off.release(); S.thist.release(); S.c_pl.release(); S.c_pt.release();
-    S.pair_counts.release(); S.chunk_range.release(); S.chunks.release(); S.n_chunks.release(); S.pair_base.release();
-    S.work.release(); S.mcnt.release(); S.mticket.release(); S.ins_blk.release(); S.ins_off.release();
-    S.h_counts.release(); S.h_work.release();
-  }
-  {
-    auto& W = c->win;
-    for (int b = 0; b < 2; ++b) { W.pl[b].release(); W.pt[b].release(); }
-    W.meta.release(); if (W.meta_ev) (void)hipEventDestroy(W.meta_ev); W.partials.release(); W.dposes.release();
-    W.pticket.release(); W.dticket.release(); W.dflag.release(); W.dbg.release(); W.hG.release(); W.hM.release(); W.hposes.release(); W.hmeta.release();
-  }
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  if (c->side) (void)hipStreamDestroy(c->side);
-  if (c->side2) (void)hipStreamDestroy(c->side2);
-  if (c->lin) (void)hipStreamDestroy(c->lin);
-  c->ev_fork.destroy();
-  c->ev_join.destroy();
-  c->ev_pf.destroy();
-  c->ev_pf_fork.destroy();
   delete c;
 }
 
@@ -1831,25 +1724,25 @@ fmx_status fmx_extract_download(fmx_ctx* c, float* planar, uint32_t* planar_inde
     const uint32_t npl = c->n_qpl, npt = c->n_qpt;
     if (planar) {
       std::vector<float4> a(npl), b(npl);
-      FMX_HIP(hipMemcpy(a.data(), c->q_pl_pos.p, npl * sizeof(float4), hipMemcpyDeviceToHost));
-      FMX_HIP(hipMemcpy(b.data(), c->q_pl_nrm.p, npl * sizeof(float4), hipMemcpyDeviceToHost));
+      FMX_HIP(hipMemcpy(a.data(), c->q.pl_pos.p, npl * sizeof(float4), hipMemcpyDeviceToHost));
+      FMX_HIP(hipMemcpy(b.data(), c->q.pl_nrm.p, npl * sizeof(float4), hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < npl; ++i) {
         planar[6 * i] = a[i].x; planar[6 * i + 1] = a[i].y; planar[6 * i + 2] = a[i].z;
         planar[6 * i + 3] = b[i].x; planar[6 * i + 4] = b[i].y; planar[6 * i + 5] = b[i].z;
       }
     }
-    if (planar_index) FMX_HIP(hipMemcpy(planar_index, c->q_pl_idx.p, npl * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (planar_index) FMX_HIP(hipMemcpy(planar_index, c->q.pl_idx.p, npl * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (point) {
       std::vector<float4> a(npt);
-      FMX_HIP(hipMemcpy(a.data(), c->q_pt_pos.p, npt * sizeof(float4), hipMemcpyDeviceToHost));
+      FMX_HIP(hipMemcpy(a.data(), c->q.pt_pos.p, npt * sizeof(float4), hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < npt; ++i) {
         point[3 * i] = a[i].x; point[3 * i + 1] = a[i].y; point[3 * i + 2] = a[i].z;
       }
     }
-    if (point_index) FMX_HIP(hipMemcpy(point_index, c->q_pt_idx.p, npt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (point_index) FMX_HIP(hipMemcpy(point_index, c->q.pt_idx.p, npt * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (planar_mask) {
       if (!c->rows) throw StatusError(FMX_E_STATE, "no device extraction");
-      FMX_HIP(hipMemcpy(planar_mask, c->planar_mask.p, (size_t)c->rows * c->cols, hipMemcpyDeviceToHost));
+      FMX_HIP(hipMemcpy(planar_mask, c->q.planar_mask.p, (size_t)c->rows * c->cols, hipMemcpyDeviceToHost));
     }
   });
 }
@@ -1938,28 +1831,28 @@ fmx_status fmx_match(fmx_ctx* c, const double pose_j[12], double max_dist, uint3
     }
     if (!cpl && !cpt) return;
     match_counts_fetch(c);
-    if (cpl) std::memcpy(cpl, c->cnt_pl.data(), c->K * sizeof(uint32_t));
-    if (cpt) std::memcpy(cpt, c->cnt_pt.data(), c->K * sizeof(uint32_t));
+    if (cpl) std::memcpy(cpl, c->m.cnt_pl.data(), c->K * sizeof(uint32_t));
+    if (cpt) std::memcpy(cpt, c->m.cnt_pt.data(), c->K * sizeof(uint32_t));
   });
 }
 
 fmx_status fmx_match_download(fmx_ctx* c, int32_t* pair, double* d2, double* pi, double* ni) {
   return guard(c, [&] {
-    if (!c->have_match) throw StatusError(FMX_E_STATE, "no match results");
+    if (!c->m.have_match) throw StatusError(FMX_E_STATE, "no match results");
     FMX_HIP(hipStreamSynchronize(c->stream));
     const uint32_t nq = c->n_qpl + c->n_qpt;
-    if (pair) FMX_HIP(hipMemcpy(pair, c->m_pair.p, nq * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (d2) FMX_HIP(hipMemcpy(d2, c->m_d2.p, nq * sizeof(double), hipMemcpyDeviceToHost));
+    if (pair) FMX_HIP(hipMemcpy(pair, c->m.m_pair.p, nq * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (d2) FMX_HIP(hipMemcpy(d2, c->m.m_d2.p, nq * sizeof(double), hipMemcpyDeviceToHost));
     if (pi) {
       std::vector<double4> a(nq);
-      FMX_HIP(hipMemcpy(a.data(), c->m_pi.p, nq * sizeof(double4), hipMemcpyDeviceToHost));
+      FMX_HIP(hipMemcpy(a.data(), c->m.m_pi.p, nq * sizeof(double4), hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < nq; ++i) {
         pi[3 * i] = a[i].x; pi[3 * i + 1] = a[i].y; pi[3 * i + 2] = a[i].z;
       }
     }
     if (ni) {
       std::vector<double4> a(c->n_qpl);
-      FMX_HIP(hipMemcpy(a.data(), c->m_ni.p, c->n_qpl * sizeof(double4), hipMemcpyDeviceToHost));
+      FMX_HIP(hipMemcpy(a.data(), c->m.m_ni.p, c->n_qpl * sizeof(double4), hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < c->n_qpl; ++i) {
         ni[3 * i] = a[i].x; ni[3 * i + 1] = a[i].y; ni[3 * i + 2] = a[i].z;
       }
@@ -1969,7 +1862,7 @@ fmx_status fmx_match_download(fmx_ctx* c, int32_t* pair, double* d2, double* pi,
 
 fmx_status fmx_map_insert(fmx_ctx* c, double min_dist_map, uint32_t* n_inserted) {
   return guard(c, [&] {
-    if (!c->have_match) throw StatusError(FMX_E_STATE, "no match results");
+    if (!c->m.have_match) throw StatusError(FMX_E_STATE, "no match results");
     if (min_dist_map != c->P.min_dist_map)
       throw StatusError(FMX_E_INVAL, "min_dist_map must equal the context's (fixed at match time)");
     ensure_pool_room(c, 0, c->n_qpl);
@@ -2055,7 +1948,7 @@ fmx_status fmx_linearize_matched(fmx_ctx* c, const double pose_j[12], double sig
       return;
     }
     settle_match(c);
-    if (!c->have_match) throw StatusError(FMX_E_STATE, "no match results");
+    if (!c->m.have_match) throw StatusError(FMX_E_STATE, "no match results");
     run_linearize_total(c, pose_j, sigma, out);
   });
 }
@@ -2154,7 +2047,7 @@ fmx_status fmx_next_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev) {
       // the slot's pinned bytes may still feed the DMA of a queued, not yet taken extraction
       if (c->pf_launched && c->pf_host && c->pf_slot == slot)
         FMX_HIP(hipStreamSynchronize(c->pf_L.st ? c->pf_L.st : c->side2));
-      stage_submit(c, c->st_pf[slot], xyzw, c->pin_pf[slot], n * sizeof(float4));
+      stage_submit(c, c->st_pf[slot], xyzw, c->pin_pf[slot].p, n * sizeof(float4));
       if (c->stager.threads() == 0) stage_finish(c, c->st_pf[slot]);
       c->ann_slot = slot;
     }
@@ -2263,11 +2156,7 @@ fmx_status fmx_scan_buffer(fmx_ctx* c, size_t n, float** out) {
         if (c->ann_ptr >= b0 && c->ann_ptr < b1) c->ann_ptr = nullptr;
         if (c->pf_launched && c->pf_ptr >= b0 && c->pf_ptr < b1) pf_drop(c);
       }
-      if (B.p) (void)hipHostFree(B.p);
-      B.p = nullptr;
-      B.cap = 0;
-      FMX_HIP(hipHostMalloc(reinterpret_cast<void**>(&B.p), n * sizeof(float4), hipHostMallocDefault));
-      B.cap = n;
+      B.alloc(n);  // frees the old buffer first
     }
     c->scanbuf_next = (c->scanbuf_next + 1) % 3;
     *out = reinterpret_cast<float*>(B.p);
@@ -2547,23 +2436,23 @@ fmx_status fmx_match_work(fmx_ctx* c, double work[3]) {
   return guard<false>(c, [&] {  // the last launched match (a fused one counts too)
     match_counts_fetch(c);
     work[0] = (double)c->n_qpl + (double)c->n_qpt;
-    work[1] = c->last_probes;
-    work[2] = c->last_cands;
+    work[1] = c->m.last_probes;
+    work[2] = c->m.last_cands;
   });
 }
 
 fmx_status fmx_match_cert(fmx_ctx* c, uint64_t counts[2], uint8_t* certified) {
   return guard(c, [&] {
-    if (!c->have_match) throw StatusError(FMX_E_STATE, "no match results");
+    if (!c->m.have_match) throw StatusError(FMX_E_STATE, "no match results");
     match_counts_fetch(c);
     if (counts) {
-      counts[0] = c->cert_tot[0];
-      counts[1] = c->cert_tot[1];
+      counts[0] = c->m.cert_tot[0];
+      counts[1] = c->m.cert_tot[1];
     }
     if (certified) {
       const uint32_t nq = c->n_qpl + c->n_qpt;
       std::vector<uint8_t> f(nq);
-      if (nq) FMX_HIP(hipMemcpy(f.data(), c->m_ins.p, nq, hipMemcpyDeviceToHost));
+      if (nq) FMX_HIP(hipMemcpy(f.data(), c->m.m_ins.p, nq, hipMemcpyDeviceToHost));
       for (uint32_t q = 0; q < nq; ++q) certified[q] = (f[q] >> 1) & 1;
     }
   });

@@ -13,6 +13,8 @@
 #include <cstdlib>
 #include <functional>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "fmx/fmx.h"
@@ -39,18 +41,35 @@ inline std::atomic<uint64_t>& dbuf_reallocs() {  // diagnostic (FMX_HOST_TIMING 
   static std::atomic<uint64_t> n{0};              // live on several host threads
   return n;
 }
+// The device and pinned-host buffers below own their storage: the destructor frees, they
+// move but do not copy (a copy would free twice), and a moved-from buffer is empty.  What
+// has to finish before a buffer may go (queued kernels, DMAs, the staging helpers) is the
+// holder's business: ~fmx_ctx drains first (fmx_api.cpp).
+//
 // Growable device buffer (grows only; contents are not preserved across growth).
 template <class T>
 struct DBuf {
   T* p = nullptr;
   size_t cap = 0;
+  DBuf() = default;
+  DBuf(const DBuf&) = delete;
+  DBuf& operator=(const DBuf&) = delete;
+  DBuf(DBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  DBuf& operator=(DBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr);
+      cap = std::exchange(o.cap, 0);
+    }
+    return *this;
+  }
+  ~DBuf() { release(); }
   void ensure(size_t n) {
     if (n <= cap) return;
     ++dbuf_reallocs();
     static const bool log = std::getenv("FMX_REALLOC_LOG") != nullptr;  // diagnostic: regrowths
     if (log && p) fprintf(stderr, "dbuf regrow %zu -> %zu elements of %zu B\n", cap, n, sizeof(T));
-    if (p) (void)hipFree(p);  // synchronizes the device: grow geometrically so it stays rare
-    p = nullptr;
+    release();  // hipFree synchronizes the device: grow geometrically so it stays rare
     // at least 256k elements (<= 8 MB for the widest element): the per-scan buffers of
     // a 128 x 2048 stream never regrow once the window has filled (a regrowth's
     // hipFree serializes the device mid-scan)
@@ -77,9 +96,24 @@ struct HBuf {  // pinned host memory, also mapped into the device address space
   T* p = nullptr;
   T* d = nullptr;  // device-visible alias: kernels write small results here directly
   size_t cap = 0;
+  HBuf() = default;
+  HBuf(const HBuf&) = delete;
+  HBuf& operator=(const HBuf&) = delete;
+  HBuf(HBuf&& o) noexcept
+      : p(std::exchange(o.p, nullptr)), d(std::exchange(o.d, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  HBuf& operator=(HBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr);
+      d = std::exchange(o.d, nullptr);
+      cap = std::exchange(o.cap, 0);
+    }
+    return *this;
+  }
+  ~HBuf() { release(); }
   void ensure(size_t n) {
     if (n <= cap) return;
-    if (p) (void)hipHostFree(p);
+    release();
     size_t c = n + n / 4 + 64;
     FMX_HIP(hipHostMalloc(&p, c * sizeof(T), hipHostMallocMapped | hipHostMallocCoherent));
     void* dp = nullptr;
@@ -89,25 +123,76 @@ struct HBuf {  // pinned host memory, also mapped into the device address space
   }
   void release() {
     if (p) (void)hipHostFree(p);
+    p = d = nullptr;
+    cap = 0;
+  }
+};
+// Plain page-locked host memory of exactly n elements (hipHostMallocDefault: DMA sources
+// the device never addresses; the staging buffers and fmx_scan_buffer).  No growth policy:
+// the holder decides when the old storage may go (drain, release(), then alloc()).  Stays
+// where it is: neither copied nor moved.
+template <class T>
+struct PinBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { release(); }
+  void alloc(size_t n) {
+    release();
+    FMX_HIP(hipHostMalloc(reinterpret_cast<void**>(&p), n * sizeof(T), hipHostMallocDefault));
+    cap = n;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
     p = nullptr;
     cap = 0;
   }
 };
+// One lazily created event (no timing).  Stays where it is.
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  hipEvent_t get() {
+    if (!e) FMX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return e;
+  }
+};
+static_assert(!std::is_copy_constructible_v<DBuf<float>> && !std::is_copy_assignable_v<DBuf<float>> &&
+                  std::is_nothrow_move_constructible_v<DBuf<float>> && std::is_nothrow_move_assignable_v<DBuf<float>>,
+              "DBuf owns its storage: move only");
+static_assert(!std::is_copy_constructible_v<HBuf<float>> && !std::is_copy_assignable_v<HBuf<float>> &&
+                  std::is_nothrow_move_constructible_v<HBuf<float>> && std::is_nothrow_move_assignable_v<HBuf<float>>,
+              "HBuf owns its storage: move only");
+static_assert(!std::is_copy_constructible_v<PinBuf<float>> && !std::is_copy_assignable_v<PinBuf<float>> &&
+                  !std::is_move_constructible_v<PinBuf<float>> && !std::is_move_assignable_v<PinBuf<float>>,
+              "PinBuf owns its storage and stays where it is");
+static_assert(!std::is_copy_constructible_v<Event> && !std::is_copy_assignable_v<Event> &&
+                  !std::is_move_constructible_v<Event> && !std::is_move_assignable_v<Event>,
+              "Event owns its handle and stays where it is");
 
 // A ring of events (fmx_ctx's cross-stream ordering): record() takes the next event,
-// last() is the most recently recorded one.
+// last() is the most recently recorded one.  Owns its events; stays where it is.
 struct EvRing {
   static constexpr int kN = 8;
   hipEvent_t e[kN] = {};
   int cur = 0;
+  EvRing() = default;
+  EvRing(const EvRing&) = delete;
+  EvRing& operator=(const EvRing&) = delete;
+  ~EvRing() {
+    for (auto& x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
   void create() {
     for (auto& x : e)
       if (!x) FMX_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-  }
-  void destroy() {
-    for (auto& x : e)
-      if (x) (void)hipEventDestroy(x);
-    for (auto& x : e) x = nullptr;
   }
   hipEvent_t record(hipStream_t st) {
     cur = (cur + 1) % kN;
@@ -116,6 +201,9 @@ struct EvRing {
   }
   hipEvent_t last() const { return e[cur]; }
 };
+static_assert(!std::is_copy_constructible_v<EvRing> && !std::is_copy_assignable_v<EvRing> &&
+                  !std::is_move_constructible_v<EvRing> && !std::is_move_assignable_v<EvRing>,
+              "EvRing owns its events and stays where it is");
 
 // Profiled kernel classes (bench.py roofline).
 enum ProfId {
@@ -157,10 +245,20 @@ struct Prof {
   // match work since the last reset, [cold, warm] x {launches, queries, probes, candidates,
   // certified queries, warm queries}
   double mwork[2][6] = {};
-  std::vector<ProfPending> pending;
+  std::vector<ProfPending> pending;      // both lists own their (timing) events
   std::vector<hipEvent_t> free_events;
   HBuf<uint32_t> wring;  // [kProfRing][4]: probes, candidates, certified, warm (pinned, mapped)
   uint32_t wnext = 0;    // next slot; slots in use = pending entries with ring >= 0
+  Prof() = default;
+  Prof(const Prof&) = delete;
+  Prof& operator=(const Prof&) = delete;
+  ~Prof() {
+    for (hipEvent_t e : free_events) (void)hipEventDestroy(e);
+    for (const ProfPending& pe : pending) {
+      (void)hipEventDestroy(pe.a);
+      (void)hipEventDestroy(pe.b);
+    }
+  }
 };
 
 // Scoped kernel timer: HIP events on the context stream around one launch group.
@@ -263,7 +361,7 @@ struct WinStore {
   DBuf<uint32_t> meta;  // [chunks (4 words each)][chunk_range]
   const Chunk* chunks_p = nullptr;
   const uint32_t* chunk_range_p = nullptr;
-  hipEvent_t meta_ev = nullptr;  // the last upload from hmeta
+  Event meta_ev;  // the last upload from hmeta
   bool meta_ev_pending = false;
   uint32_t nch = 0;
   int npairs = 0;
@@ -282,32 +380,57 @@ struct WinStore {
   HBuf<uint32_t> hmeta;
 };
 
-// A second set of match outputs: register_scan launches speculative matches into it
-// (on the side stream) and swaps it in when the speculation was right (fmx_api.cpp,
-// swap_match_set).  The members mirror fmx_ctx's match results one to one.
+// Everything one match produces: the query-indexed results (planar then point), the
+// sorted correspondences with their chunk table, and the launch's bookkeeping.  fmx_ctx
+// holds two: `m`, which every entry point and launcher reads and writes, and `spec`, into
+// which register_scan launches speculative matches; the two are exchanged whole when a
+// speculation was right (fmx_api.cpp, swap_match_set).  A member added here is thereby in
+// both sets and in the exchange.  What a match rewrites in place in stream order (m_rec,
+// m_cell, the warm-start and certificate state) is not per set and stays on the context.
 struct MatchSet {
   DBuf<int32_t> m_pair;
   DBuf<double> m_d2;
   DBuf<double4> m_pi, m_ni;
   DBuf<uint8_t> m_ins;
-  DBuf<uint32_t> hist, hist_off, thist;
-  uint32_t thist_par = 0;
-  DBuf<double> c_pl, c_pt;
-  DBuf<uint32_t> pair_counts, chunk_range;
+  DBuf<uint32_t> hist, hist_off;
+  DBuf<uint32_t> thist;    // tiled pair sort: per-(type, pair, tile) counts, two halves
+  uint32_t thist_par = 0;  // the half the last tiled match added into
+  // sorted correspondences (pair-major SoA) + chunk table
+  DBuf<double> c_pl, c_pt;   // [9][cap_pl], [6][cap_pt]
+  DBuf<uint32_t> pair_counts;  // [2][K] plane rows, point pairs
+  DBuf<uint32_t> chunk_range;  // [K+1]
   DBuf<Chunk> chunks;
-  DBuf<uint32_t> n_chunks, pair_base, work, mcnt, mticket, ins_blk, ins_off;
+  DBuf<uint32_t> n_chunks;
+  DBuf<uint32_t> pair_base;      // [2][K] first row of each pair
+  DBuf<uint32_t> work;           // match work counters per block (probes, candidates)
+  DBuf<uint32_t> mcnt, mticket;  // query-order match: per-pair counters + ticket
+  DBuf<uint32_t> ins_blk, ins_off;  // per match block insert counts / offsets
   HBuf<uint32_t> h_counts, h_work;
-  bool have_match = false, have_corr = false, scatter_pending = false, counts_pending = false, have_qo = false;
+  bool have_match = false, have_corr = false, have_qo = false;
+  bool scatter_pending = false;  // the sorted match's scatter (ps) not yet launched (deferred by fmx_match)
+  bool counts_pending = false;
   size_t ld_pl = 0, ld_pt = 0;
-  uint32_t max_chunks = 0, work_blocks = 0, match_nb_pl = 0, match_nb = 0, n_qo = 0;
-  bool work_copied = false;
-  int match_group = 8;
-  PairScatter ps;
-  uint64_t rows_pl = 0, rows_pt = 0;
-  std::vector<uint32_t> cnt_pl, cnt_pt;
+  uint32_t max_chunks = 0, work_blocks = 0;
+  uint32_t match_nb_pl = 0, match_nb = 0;  // blocks of the last match
+  uint32_t n_qo = 0;                       // queries of the last query-order match
+  bool work_copied = false;  // h_work holds the last match's counters (profiling was on)
+  int match_group = 8;       // lanes per query of the last run_match (voxelmap.hip g8 / gl)
+  PairScatter ps;            // the last sorted match's scatter (voxelmap.hip)
+  uint64_t rows_pl = 0, rows_pt = 0;      // correspondences (plane rows, point pairs)
+  std::vector<uint32_t> cnt_pl, cnt_pt;   // per pair, host copy after match
   double last_probes = 0, last_cands = 0;
-  uint32_t ins_tot[2] = {0, 0};
-  uint32_t cert_tot[2] = {0, 0};
+  uint32_t ins_tot[2] = {0, 0};   // insert totals of the last match
+  uint32_t cert_tot[2] = {0, 0};  // ... its certified / warm query counts
+};
+
+// The features one extraction leaves for the matches: planar positions + normals, point
+// positions, each feature's index in the scan, and the scan's planar mask.  fmx_ctx holds two:
+// `q` of the scan being registered and `nq`, which the pipelined extraction of the
+// announced next scan fills (fmx_api.cpp, swap_query_set).
+struct QuerySet {
+  DBuf<float4> pl_pos, pl_nrm, pt_pos;
+  DBuf<uint32_t> pl_idx, pt_idx;
+  DBuf<uint8_t> planar_mask;
 };
 
 // An extraction launched on stream `st`: its totals and completion word go to mapped
@@ -325,6 +448,13 @@ struct ExLaunch {
 constexpr int kStatsN = 14;  // fmx_last_stats entries
 
 struct fmx_ctx {
+  fmx_ctx() = default;
+  fmx_ctx(const fmx_ctx&) = delete;
+  fmx_ctx& operator=(const fmx_ctx&) = delete;
+  // drains the streams, stops the helpers, then est / comm / streams; the members below
+  // free themselves afterwards (fmx_api.cpp)
+  ~fmx_ctx();
+
   fmx_params P{};
   int device = 0;
   hipStream_t stream = nullptr;
@@ -342,7 +472,6 @@ struct fmx_ctx {
 
   // ---- extraction scratch
   fmx::DBuf<float4> scan;
-  fmx::DBuf<uint8_t> planar_mask;
   fmx::DBuf<uint32_t> sel_slots, pt_slots, row_counts, row_ok, row_off;
   fmx::DBuf<int2> closest;
   fmx::DBuf<float4> nrm_slots, blk_lo, blk_hi;
@@ -354,16 +483,13 @@ struct fmx_ctx {
   // ---- current query set (scan being registered)
   uint64_t q_scan = 0;
   uint32_t n_qpl = 0, n_qpt = 0, n_sel = 0;
-  fmx::DBuf<float4> q_pl_pos, q_pl_nrm, q_pt_pos;
-  fmx::DBuf<uint32_t> q_pl_idx, q_pt_idx;
+  fmx::QuerySet q;
   bool have_queries = false;
 
   // ---- pipelined extraction (fmx_next_scan): the scan after the one being registered
-  // is extracted on the side stream, during this registration, into a second query set
-  // (+ planar mask); the next register_scan swaps it in instead of extracting
-  fmx::DBuf<float4> nq_pl_pos, nq_pl_nrm, nq_pt_pos;
-  fmx::DBuf<uint32_t> nq_pl_idx, nq_pt_idx;
-  fmx::DBuf<uint8_t> n_planar_mask;
+  // is extracted on the side stream, during this registration, into the second query
+  // set; the next register_scan swaps it in instead of extracting
+  fmx::QuerySet nq;
   const float* ann_ptr = nullptr;   // announced by fmx_next_scan (device pointer), its size
   size_t ann_n = 0;
   const float* pf_ptr = nullptr;    // the scan whose extraction is queued on the side stream
@@ -382,8 +508,7 @@ struct fmx_ctx {
   // + extracted on side2 once its copy has finished.
   fmx::Stager stager;
   fmx::StageReq st_seq, st_pf[2];
-  uint8_t* pin_seq = nullptr;
-  uint8_t* pin_pf[2] = {nullptr, nullptr};
+  fmx::PinBuf<uint8_t> pin_seq, pin_pf[2];
   size_t pin_cap = 0;           // bytes of each pinned staging buffer
   bool ann_host = false;        // the announced scan is host memory (staged in st_pf[ann_slot])
   bool ann_pinned = false;      // ... page-locked: DMA'd from the caller's memory, no staging
@@ -391,10 +516,7 @@ struct fmx_ctx {
   bool pf_host = false;         // the queued extraction's scan was host memory
   fmx::DBuf<float4> pf_scan;    // device copy of a host-announced scan (side2 order)
   fmx::DBuf<float> scan3, pf_scan3;  // packed x, y, z of staged host scans (DMA targets)
-  struct ScanBuf {              // fmx_scan_buffer: pinned scan buffers handed to the caller
-    float4* p = nullptr;
-    size_t cap = 0;
-  } scanbuf[3];
+  fmx::PinBuf<float4> scanbuf[3];  // fmx_scan_buffer: pinned scan buffers handed to the caller
   int scanbuf_next = 0;
 
   // ---- scan deskewing (deskew.hip; fmx_deskew_configure).  Off unless configured: no
@@ -456,12 +578,8 @@ struct fmx_ctx {
   bool map_err_checked = false;   // ... already read back (once per build)
   fmx::HBuf<unsigned long long> h_mapinfo;  // pinned: epoch << 32 | dense cells of the last finished build
 
-  // ---- match results (query-indexed; planar then point)
-  fmx::DBuf<int32_t> m_pair;
-  fmx::DBuf<double> m_d2;
-  fmx::DBuf<double4> m_pi, m_ni;
-  fmx::DBuf<uint8_t> m_ins;
-  fmx::DBuf<uint32_t> hist, hist_off;
+  // ---- match results: the current set (fmx::MatchSet; `spec` below is the other one)
+  fmx::MatchSet m;
   // Warm start: every match writes its NN record per query (m_rec, not part of a
   // MatchSet: each launch reads and rewrites it in place, in stream order).  A later
   // match on the same map and query set starts each query's search bounded by that
@@ -470,38 +588,15 @@ struct fmx_ctx {
   fmx::DBuf<uint4> m_cell;    // per query: its own cell as the last match found it (same scheme)
   uint64_t warm_gen = 1;      // bumped by every map build and query-set change
   uint64_t warm_rec_gen = 0;  // warm_gen when m_rec was last written (0: never)
-  fmx::DBuf<uint32_t> thist;  // tiled pair sort: per-(type, pair, tile) counts, two halves
-  uint32_t thist_par = 0;     // the half the last tiled match added into
   fmx::DBuf<float> cert_b2;   // FMX_CERT_DIAG / FMX_WARM_CERT builds: per query the last match's second-best bound
   double cert_pose[12] = {};  // ... and that match's pose
   uint64_t cert_gen = 0;      // warm_gen when cert_b2 was last written by an 8-lane match (0: none)
-  bool have_match = false;
 
-  // ---- sorted correspondences (pair-major SoA) + chunk table
+  // ---- sorted correspondences: what is not per match set
   uint32_t K = 0;
   uint64_t corr_gen = 0;         // bumped by every call that replaces the correspondences (fmx_corr_generation)
-  fmx::DBuf<double> c_pl, c_pt;  // [9][cap_pl], [6][cap_pt]
-  size_t ld_pl = 0, ld_pt = 0;
-  fmx::DBuf<uint32_t> pair_counts;  // [2][K] plane rows, point pairs
-  fmx::DBuf<uint32_t> chunk_range;  // [K+1]
-  fmx::DBuf<fmx::Chunk> chunks;
-  fmx::DBuf<uint32_t> n_chunks;
-  uint32_t max_chunks = 0;
-  int match_group = 8;  // lanes per query of the last run_match (voxelmap.hip g8 / gl)
-  bool have_corr = false;
-  fmx::PairScatter ps;          // the last sorted match's scatter (voxelmap.hip)
-  bool scatter_pending = false; // ... not yet launched (deferred by fmx_match)
-  uint64_t rows_pl = 0, rows_pt = 0;           // correspondences (plane rows, point pairs)
-  std::vector<uint32_t> cnt_pl, cnt_pt;         // per pair, host copy after match
   fmx::HBuf<double> h_corr;
-  fmx::HBuf<uint32_t> h_meta, h_counts;
-  fmx::DBuf<uint32_t> pair_base;                // [2][K] first row of each pair
-  fmx::DBuf<uint32_t> work;                     // match work counters per block (probes, candidates)
-  fmx::HBuf<uint32_t> h_work;
-  uint32_t work_blocks = 0;
-  bool work_copied = false;  // h_work holds the last match's counters (profiling was on)
-  double last_probes = 0, last_cands = 0;
-  bool counts_pending = false;
+  fmx::HBuf<uint32_t> h_meta;
   bool nrm_attr_set = false;
   bool lds_attr_set = false;
 
@@ -509,20 +604,13 @@ struct fmx_ctx {
   fmx::DBuf<double> bpart;                        // k_linearize_total block partials
   fmx::DBuf<uint32_t> ticket;                     // its last-block ticket
   fmx::DBuf<uint32_t> fz_tickets;                 // fused match + linearization: per block-group tickets
-  fmx::DBuf<uint32_t> mcnt, mticket;              // query-order match: per-pair counters + ticket
   bool fz_work_pending = false;                   // fused launch's work counters copied, not yet summed
   fmx::DBuf<uint32_t> fz_work;                    // ... its own per-block work words (a settled match's
-  fmx::HBuf<uint32_t> fz_h_work;                  // work / h_work may still await match_counts_fetch)
+  fmx::HBuf<uint32_t> fz_h_work;                  // m.work / m.h_work may still await match_counts_fetch)
   uint32_t fz_work_blocks = 0;
-  fmx::DBuf<uint32_t> ins_blk, ins_off;           // per match block insert counts / offsets
-  uint32_t ins_tot[2] = {0, 0};                   // insert totals of the last match
-  uint32_t cert_tot[2] = {0, 0};                  // ... its certified / warm query counts
   fmx::DBuf<uint32_t> mprof;                      // profiled match launches' probe / candidate sums (self-resetting)
-  uint32_t match_nb_pl = 0, match_nb = 0;         // blocks of the last match
-  uint32_t n_qo = 0;                              // queries of the last query-order match
   fmx::HBuf<uint32_t> h_flag;                     // mapped completion word (wait_flag)
   uint32_t flag_seq = 0;
-  bool have_qo = false;
   // fmx_match without count outputs on a large query set is not launched at once: if
   // the next consumer is fmx_linearize_matched at the same pose, match and
   // linearization run fused (no per-query results); any other consumer launches the
@@ -784,7 +872,7 @@ inline uint32_t next_flag(fmx_ctx* c) {
 }
 // voxelmap.hip is built twice: 8 lanes per query (fmx::g8, per-scan query sets) and 1
 // (fmx::gl, large query sets: more queries in flight per wave); the fmx:: entry points
-// below dispatch on c->match_group, chosen by run_match.
+// below dispatch on c->m.match_group, chosen by run_match.
 #define FMX_VM_DECLS                                                                                   \
   void run_map_build(fmx_ctx* c, const std::vector<uint64_t>& scans, const double* poses34, double w, \
                      hipStream_t st = nullptr);                                                      \

@@ -172,26 +172,26 @@ void upload_corr(fmx_ctx* c, uint32_t K, const uint32_t* np, const double* ppi, 
     Nt += nt[k];
   }
   c->K = K;
-  c->ld_pl = Np + 1;
-  c->ld_pt = Nt + 1;
-  c->c_pl.ensure(9 * c->ld_pl);
-  c->c_pt.ensure(6 * c->ld_pt);
-  c->h_corr.ensure(9 * c->ld_pl + 6 * c->ld_pt);
+  c->m.ld_pl = Np + 1;
+  c->m.ld_pt = Nt + 1;
+  c->m.c_pl.ensure(9 * c->m.ld_pl);
+  c->m.c_pt.ensure(6 * c->m.ld_pt);
+  c->h_corr.ensure(9 * c->m.ld_pl + 6 * c->m.ld_pt);
   double* hp = c->h_corr.p;
-  double* ht = hp + 9 * c->ld_pl;
+  double* ht = hp + 9 * c->m.ld_pl;
   for (uint64_t r = 0; r < Np; ++r)
     for (int d = 0; d < 3; ++d) {
-      hp[d * c->ld_pl + r] = ppi[3 * r + d];
-      hp[(3 + d) * c->ld_pl + r] = pni[3 * r + d];
-      hp[(6 + d) * c->ld_pl + r] = ppj[3 * r + d];
+      hp[d * c->m.ld_pl + r] = ppi[3 * r + d];
+      hp[(3 + d) * c->m.ld_pl + r] = pni[3 * r + d];
+      hp[(6 + d) * c->m.ld_pl + r] = ppj[3 * r + d];
     }
   for (uint64_t r = 0; r < Nt; ++r)
     for (int d = 0; d < 3; ++d) {
-      ht[d * c->ld_pt + r] = tpi[3 * r + d];
-      ht[(3 + d) * c->ld_pt + r] = tpj[3 * r + d];
+      ht[d * c->m.ld_pt + r] = tpi[3 * r + d];
+      ht[(3 + d) * c->m.ld_pt + r] = tpj[3 * r + d];
     }
-  FMX_HIP(hipMemcpyAsync(c->c_pl.p, hp, 9 * c->ld_pl * sizeof(double), hipMemcpyHostToDevice, st));
-  FMX_HIP(hipMemcpyAsync(c->c_pt.p, ht, 6 * c->ld_pt * sizeof(double), hipMemcpyHostToDevice, st));
+  FMX_HIP(hipMemcpyAsync(c->m.c_pl.p, hp, 9 * c->m.ld_pl * sizeof(double), hipMemcpyHostToDevice, st));
+  FMX_HIP(hipMemcpyAsync(c->m.c_pt.p, ht, 6 * c->m.ld_pt * sizeof(double), hipMemcpyHostToDevice, st));
   // chunk table (pair-major), the layout the sorted match's last block writes
   std::vector<Chunk> ch;
   std::vector<uint32_t> cr(K + 1);
@@ -207,10 +207,10 @@ void upload_corr(fmx_ctx* c, uint32_t K, const uint32_t* np, const double* ppi, 
   }
   cr[K] = (uint32_t)ch.size();
   const uint32_t nch = (uint32_t)ch.size();
-  c->chunks.ensure(nch + 1);
-  c->chunk_range.ensure(K + 1);
-  c->n_chunks.ensure(1);
-  c->pair_counts.ensure(2 * (size_t)K + 1);
+  c->m.chunks.ensure(nch + 1);
+  c->m.chunk_range.ensure(K + 1);
+  c->m.n_chunks.ensure(1);
+  c->m.pair_counts.ensure(2 * (size_t)K + 1);
   c->h_meta.ensure(4 * (size_t)nch + 2 * (K + 1) + 2 * (size_t)K + 4);
   uint32_t* hm = c->h_meta.p;
   std::memcpy(hm, ch.data(), nch * sizeof(Chunk));
@@ -218,18 +218,18 @@ void upload_corr(fmx_ctx* c, uint32_t K, const uint32_t* np, const double* ppi, 
   hm[4 * nch + K + 1] = nch;
   std::memcpy(hm + 4 * nch + K + 2, np, K * sizeof(uint32_t));
   std::memcpy(hm + 4 * nch + 2 * K + 2, nt, K * sizeof(uint32_t));
-  FMX_HIP(hipMemcpyAsync(c->chunks.p, hm, nch * sizeof(Chunk), hipMemcpyHostToDevice, st));
-  FMX_HIP(hipMemcpyAsync(c->chunk_range.p, hm + 4 * nch, (K + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  FMX_HIP(hipMemcpyAsync(c->n_chunks.p, hm + 4 * nch + K + 1, sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  FMX_HIP(hipMemcpyAsync(c->pair_counts.p, hm + 4 * nch + K + 2, 2 * K * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  FMX_HIP(hipMemcpyAsync(c->m.chunks.p, hm, nch * sizeof(Chunk), hipMemcpyHostToDevice, st));
+  FMX_HIP(hipMemcpyAsync(c->m.chunk_range.p, hm + 4 * nch, (K + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  FMX_HIP(hipMemcpyAsync(c->m.n_chunks.p, hm + 4 * nch + K + 1, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  FMX_HIP(hipMemcpyAsync(c->m.pair_counts.p, hm + 4 * nch + K + 2, 2 * K * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   FMX_HIP(hipStreamSynchronize(st));  // staging buffers may be reused after return
-  c->max_chunks = std::max<uint32_t>(nch, 1);
-  c->rows_pl = Np;
-  c->rows_pt = Nt;
-  c->counts_pending = false;
-  c->have_corr = true;
-  c->scatter_pending = false;
-  c->have_match = false;
+  c->m.max_chunks = std::max<uint32_t>(nch, 1);
+  c->m.rows_pl = Np;
+  c->m.rows_pt = Nt;
+  c->m.counts_pending = false;
+  c->m.have_corr = true;
+  c->m.scatter_pending = false;
+  c->m.have_match = false;
 }
 
 }  // namespace fmx
@@ -241,30 +241,30 @@ namespace fmx {
 // resets it)
 constexpr uint32_t kTotTargetWaves = 8192;  // waves enough to fill the chip; beyond, chunks per wave grow
 static uint32_t tot_chunks_per_wave(fmx_ctx* c) {
-  const uint32_t nch = (c->n_qo + kWave - 1) / kWave;
+  const uint32_t nch = (c->m.n_qo + kWave - 1) / kWave;
   return std::max<uint32_t>((nch + kTotTargetWaves - 1) / kTotTargetWaves, 1);
 }
 static uint32_t tot_blocks(fmx_ctx* c) {
-  const uint32_t nch = (c->n_qo + kWave - 1) / kWave, cpw = tot_chunks_per_wave(c);
+  const uint32_t nch = (c->m.n_qo + kWave - 1) / kWave, cpw = tot_chunks_per_wave(c);
   const uint32_t nblk = std::max<uint32_t>((nch + kTotWaves * cpw - 1) / (kTotWaves * cpw), 1);
   c->bpart.ensure((size_t)nblk * kTotLd);
   ensure_zeroed(c->ticket, 1, c->stream);
   return nblk;
 }
 static QoRows qo_rows(fmx_ctx* c) {
-  return QoRows{c->m_pair.p, reinterpret_cast<const double4*>(c->m_pi.p), reinterpret_cast<const double4*>(c->m_ni.p),
-                c->q_pl_pos.p, c->q_pt_pos.p, c->n_qpl, c->n_qo};
+  return QoRows{c->m.m_pair.p, reinterpret_cast<const double4*>(c->m.m_pi.p), reinterpret_cast<const double4*>(c->m.m_ni.p),
+                c->q.pl_pos.p, c->q.pt_pos.p, c->n_qpl, c->m.n_qo};
 }
 
 // register_scan's single-pose linearization: out[0..27] = sum over pairs of the packed
 // 7 x 7 [H_j b]^T [H_j b] at pose_j, out[28] = error.  One launch, one wait.
 void run_linearize_total(fmx_ctx* c, const double* pose_j34, double sigma, double* out) {
   if (!c->have_map) throw StatusError(FMX_E_STATE, "no map");
-  if (!c->have_qo) throw StatusError(FMX_E_STATE, "no query-order match");
+  if (!c->m.have_qo) throw StatusError(FMX_E_STATE, "no query-order match");
   comm_check(c);
   hipStream_t st = c->stream;
   for (int i = 0; i < 29; ++i) out[i] = 0.0;
-  if ((c->K == 0 || c->n_qo == 0) && !c->comm) return;  // sharded: every rank joins the collective
+  if ((c->K == 0 || c->m.n_qo == 0) && !c->comm) return;  // sharded: every rank joins the collective
   const uint32_t nblk = tot_blocks(c);
   Pose34 tjv;
   std::memcpy(tjv.m, pose_j34, sizeof(tjv.m));
@@ -276,11 +276,11 @@ void run_linearize_total(fmx_ctx* c, const double* pose_j34, double sigma, doubl
   const uint32_t seq = next_flag(c);  // allocates the word on first use
   double* dst = comm ? c->d_sum.p : c->h_G.d;
   uint32_t* flag = comm ? nullptr : c->h_flag.d;
-  if (c->counts_pending && c->prof.on) match_counts_fetch(c);  // exact byte model for the profile
+  if (c->m.counts_pending && c->prof.on) match_counts_fetch(c);  // exact byte model for the profile
   {
     // bytes: pair id per query + (p_i, n_i 32 B each, p_j 16 B) per accepted plane row,
     // (p_i 32 B, p_j 16 B) per accepted point pair
-    ProfScope ps(c->prof, PROF_LINEARIZE, 4.0 * c->n_qo + 80.0 * c->rows_pl + 48.0 * c->rows_pt, st);
+    ProfScope ps(c->prof, PROF_LINEARIZE, 4.0 * c->m.n_qo + 80.0 * c->m.rows_pl + 48.0 * c->m.rows_pt, st);
     hipLaunchKernelGGL(k_linearize_total, dim3(nblk), dim3(kTotWaves * kWave), 0, st, qo_rows(c), c->map_poses_p,
                        1.0 / sigma, c->bpart.p, c->ticket.p, dst, tjv, flag, seq, tot_chunks_per_wave(c));
     FMX_HIP(hipGetLastError());

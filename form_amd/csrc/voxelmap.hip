@@ -2751,16 +2751,16 @@ void run_map_build(fmx_ctx* c, const std::vector<uint64_t>& scans, const double*
   }
   delete hs_l;
   c->have_map = true;
-  c->have_match = false;
-  c->have_qo = false;
+  c->m.have_match = false;
+  c->m.have_qo = false;
 }
 
 // The pair-major row scatter of the last sorted match (k_pair_scatter_t over the
 // tiles, or k_pair_scatter per match block for windows wider than kTileMaxPairs).
 void run_pair_scatter(fmx_ctx* c) {
-  if (!c->scatter_pending) return;
-  c->scatter_pending = false;
-  const PairScatter& s = c->ps;
+  if (!c->m.scatter_pending) return;
+  c->m.scatter_pending = false;
+  const PairScatter& s = c->m.ps;
   const uint32_t nb = s.nb_pl + s.nb_pt;
   hipStream_t st = c->stream;
   if (nb > 0 && s.tiles == kTilesScatter) {  // tile blocks (if any pair) + the meta block
@@ -2770,27 +2770,27 @@ void run_pair_scatter(fmx_ctx* c) {
     a.ntl_pl = c->K ? s.ntl_pl : 0u;
     a.ntl_pt = c->K ? s.ntl_pt : 0u;
     a.K = (int)c->K;
-    a.m_pair = c->m_pair.p;
-    a.m_pi = c->m_pi.p;
-    a.m_ni = c->m_ni.p;
-    a.q_pl = c->q_pl_pos.p;
-    a.q_pt = c->q_pt_pos.p;
-    a.thist = c->thist.p + s.thist_off;
-    a.c_pl = c->c_pl.p;
-    a.ld_pl = c->ld_pl;
-    a.c_pt = c->c_pt.p;
-    a.ld_pt = c->ld_pt;
-    a.pair_counts = c->pair_counts.p;
-    a.pair_base = c->pair_base.p;
-    a.chunk_range = c->chunk_range.p;
-    a.chunks = c->chunks.p;
-    a.n_chunks = c->n_chunks.p;
-    a.host_counts = c->h_counts.d;
-    a.ins_blk = c->ins_blk.p;
-    a.ins_off = c->ins_off.p;
+    a.m_pair = c->m.m_pair.p;
+    a.m_pi = c->m.m_pi.p;
+    a.m_ni = c->m.m_ni.p;
+    a.q_pl = c->q.pl_pos.p;
+    a.q_pt = c->q.pt_pos.p;
+    a.thist = c->m.thist.p + s.thist_off;
+    a.c_pl = c->m.c_pl.p;
+    a.ld_pl = c->m.ld_pl;
+    a.c_pt = c->m.c_pt.p;
+    a.ld_pt = c->m.ld_pt;
+    a.pair_counts = c->m.pair_counts.p;
+    a.pair_base = c->m.pair_base.p;
+    a.chunk_range = c->m.chunk_range.p;
+    a.chunks = c->m.chunks.p;
+    a.n_chunks = c->m.n_chunks.p;
+    a.host_counts = c->m.h_counts.d;
+    a.ins_blk = c->m.ins_blk.p;
+    a.ins_off = c->m.ins_off.p;
     a.nb_pl = s.nb_pl;
     a.nb_pt = s.nb_pt;
-    a.work = c->work.p;
+    a.work = c->m.work.p;
     a.prof_work = s.prof_work;
     ProfScope ps(c->prof, PROF_PAIR_SORT, 0.0, st);
     hipLaunchKernelGGL(k_pair_scatter_s, dim3(a.ntl_pl + a.ntl_pt + 1), dim3(kTileQ), 0, st, a);
@@ -2801,14 +2801,14 @@ void run_pair_scatter(fmx_ctx* c) {
   ProfScope ps(c->prof, PROF_PAIR_SORT, 0.0, st);
   if (s.tiles)
     hipLaunchKernelGGL(k_pair_scatter_t, dim3(s.ntl_pl + s.ntl_pt), dim3(kTileQ), 0, st, c->n_qpl, c->n_qpt, s.ntl_pl,
-                       s.ntl_pt, s.K, c->m_pair.p, c->m_pi.p, c->m_ni.p, c->q_pl_pos.p, c->q_pt_pos.p, c->hist_off.p,
-                       c->c_pl.p, c->ld_pl, c->c_pt.p, c->ld_pt);
+                       s.ntl_pt, s.K, c->m.m_pair.p, c->m.m_pi.p, c->m.m_ni.p, c->q.pl_pos.p, c->q.pt_pos.p, c->m.hist_off.p,
+                       c->m.c_pl.p, c->m.ld_pl, c->m.c_pt.p, c->m.ld_pt);
   else if (kQPB > kWave)  // (match_group_for sends wide windows to the g8 build)
     throw StatusError(FMX_E_STATE, "per-block pair scatter needs one wave per match block");
   else
-    hipLaunchKernelGGL(k_pair_scatter, dim3(nb), dim3(kQPB), 0, st, c->n_qpl, c->n_qpt, s.nb_pl, s.K, c->m_pair.p,
-                       c->m_pi.p, c->m_ni.p, c->q_pl_pos.p, c->q_pt_pos.p, c->hist_off.p, s.nb_pt, c->pair_base.p,
-                       c->c_pl.p, c->ld_pl, c->c_pt.p, c->ld_pt);
+    hipLaunchKernelGGL(k_pair_scatter, dim3(nb), dim3(kQPB), 0, st, c->n_qpl, c->n_qpt, s.nb_pl, s.K, c->m.m_pair.p,
+                       c->m.m_pi.p, c->m.m_ni.p, c->q.pl_pos.p, c->q.pt_pos.p, c->m.hist_off.p, s.nb_pt, c->m.pair_base.p,
+                       c->m.c_pl.p, c->m.ld_pl, c->m.c_pt.p, c->m.ld_pt);
   FMX_HIP(hipGetLastError());
 }
 
@@ -2865,43 +2865,43 @@ void run_match(fmx_ctx* c, const double* pose_j34, double max_dist, double min_d
   const uint64_t tab = (uint64_t)c->K * (a.ntl_pl + a.ntl_pt);
   a.tiles = !sorted || c->K > (uint32_t)kTileMaxPairs ? 0 : tab <= kScatterTab ? kTilesScatter : kTilesTail;
   const uint32_t nq = c->n_qpl + c->n_qpt;
-  c->m_pair.ensure(nq + 1);
-  c->m_d2.ensure(nq + 1);
-  c->m_pi.ensure(nq + 1);
-  c->m_ni.ensure(c->n_qpl + 1);
-  c->m_ins.ensure(nq + 1);
+  c->m.m_pair.ensure(nq + 1);
+  c->m.m_d2.ensure(nq + 1);
+  c->m.m_pi.ensure(nq + 1);
+  c->m.m_ni.ensure(c->n_qpl + 1);
+  c->m.m_ins.ensure(nq + 1);
   const uint32_t nb = a.nb_pl + nb_pt;
-  c->hist.ensure((size_t)(nb + 1) * K);
-  c->hist_off.ensure((size_t)(nb + 1) * K);
-  c->pair_counts.ensure(2 * (size_t)K);
-  c->h_counts.ensure(2 * (size_t)K + 4);
-  c->pair_base.ensure(2 * (size_t)K);
-  c->chunk_range.ensure(K + 1);
+  c->m.hist.ensure((size_t)(nb + 1) * K);
+  c->m.hist_off.ensure((size_t)(nb + 1) * K);
+  c->m.pair_counts.ensure(2 * (size_t)K);
+  c->m.h_counts.ensure(2 * (size_t)K + 4);
+  c->m.pair_base.ensure(2 * (size_t)K);
+  c->m.chunk_range.ensure(K + 1);
   const uint32_t maxch = c->n_qpl / kPlaneChunk + c->n_qpt / kPointChunk + 2 * K + 2;
-  c->chunks.ensure(maxch);
-  c->n_chunks.ensure(1);
-  c->max_chunks = maxch;
-  c->ld_pl = c->n_qpl + 1;
-  c->ld_pt = c->n_qpt + 1;
-  c->c_pl.ensure(9 * c->ld_pl);
-  c->c_pt.ensure(6 * c->ld_pt);
-  c->work.ensure(kWorkWords * (size_t)nb + 8);
-  c->work_blocks = nb;
-  ensure_zeroed(c->mcnt, 2 * (size_t)K, st);
-  ensure_zeroed(c->mticket, 1, st);
-  c->ins_blk.ensure(nb + 1);
-  c->ins_off.ensure(nb + 1);
+  c->m.chunks.ensure(maxch);
+  c->m.n_chunks.ensure(1);
+  c->m.max_chunks = maxch;
+  c->m.ld_pl = c->n_qpl + 1;
+  c->m.ld_pt = c->n_qpt + 1;
+  c->m.c_pl.ensure(9 * c->m.ld_pl);
+  c->m.c_pt.ensure(6 * c->m.ld_pt);
+  c->m.work.ensure(kWorkWords * (size_t)nb + 8);
+  c->m.work_blocks = nb;
+  ensure_zeroed(c->m.mcnt, 2 * (size_t)K, st);
+  ensure_zeroed(c->m.mticket, 1, st);
+  c->m.ins_blk.ensure(nb + 1);
+  c->m.ins_off.ensure(nb + 1);
   // the count table in two halves: a tiled launch adds into one and clears the other
   // (read by this set's previous tiled match or its scatter) for the next
-  ensure_zeroed(c->thist, 2 * ((size_t)K * (a.ntl_pl + a.ntl_pt) + 1), st);
-  const size_t half = c->thist.cap / 2;
-  if (a.tiles && nb > 0) c->thist_par ^= 1u;  // (no launch without queries: nothing added or cleared)
-  uint32_t* thist_cur = c->thist.p + c->thist_par * half;
-  a.thist_clear = c->thist.p + (1u - c->thist_par) * half;
+  ensure_zeroed(c->m.thist, 2 * ((size_t)K * (a.ntl_pl + a.ntl_pt) + 1), st);
+  const size_t half = c->m.thist.cap / 2;
+  if (a.tiles && nb > 0) c->m.thist_par ^= 1u;  // (no launch without queries: nothing added or cleared)
+  uint32_t* thist_cur = c->m.thist.p + c->m.thist_par * half;
+  a.thist_clear = c->m.thist.p + (1u - c->m.thist_par) * half;
   a.thist_clear_n = a.tiles ? (uint32_t)half : 0u;
-  c->hist_off.ensure((size_t)K * (a.ntl_pl + a.ntl_pt) + 1);
-  const SortOut so{c->hist_off.p, c->pair_counts.p, c->pair_base.p, c->chunk_range.p, c->chunks.p, c->n_chunks.p};
-  c->h_counts.ensure(2 * (size_t)K + 4);
+  c->m.hist_off.ensure((size_t)K * (a.ntl_pl + a.ntl_pt) + 1);
+  const SortOut so{c->m.hist_off.p, c->m.pair_counts.p, c->m.pair_base.p, c->m.chunk_range.p, c->m.chunks.p, c->m.n_chunks.p};
+  c->m.h_counts.ensure(2 * (size_t)K + 4);
   auto view = [&](int t) {  // type t's table section over the shared record arrays
     VoxMap& M = c->map;
     return MapView{reinterpret_cast<const Brick*>(M.table.p) + (t == 0 ? 0 : M.cap[0]), M.cap[t] ? M.cap[t] - 1 : 0,
@@ -2935,54 +2935,54 @@ void run_match(fmx_ctx* c, const double* pose_j34, double max_dist, double min_d
     {
       auto kern = dense ? k_match<true> : k_match<false>;
       hipLaunchKernelGGL(kern, dim3(nb), dim3(kMatchThreads), K * sizeof(uint32_t), st, a,
-                         view(0), view(1), c->q_pl_pos.p, c->q_pt_pos.p, c->map_inv_p, c->m_pair.p, c->m_d2.p, c->m_pi.p,
-                         c->m_ni.p, c->m_ins.p, c->hist.p, c->work.p, c->mcnt.p, c->mticket.p, c->h_counts.d,
-                         c->ins_blk.p, c->ins_off.p, thist_cur, so, FusedArgs{});
+                         view(0), view(1), c->q.pl_pos.p, c->q.pt_pos.p, c->map_inv_p, c->m.m_pair.p, c->m.m_d2.p, c->m.m_pi.p,
+                         c->m.m_ni.p, c->m.m_ins.p, c->m.hist.p, c->m.work.p, c->m.mcnt.p, c->m.mticket.p, c->m.h_counts.d,
+                         c->m.ins_blk.p, c->m.ins_off.p, thist_cur, so, FusedArgs{});
       FMX_HIP(hipGetLastError());
     }
   }
   // no queries: no launch, so zero the counts and insert totals the kernel would write
-  if (nb == 0) FMX_HIP(hipMemsetAsync(c->h_counts.d, 0, (2 * (size_t)c->K + 4) * sizeof(uint32_t), st));
-  c->match_nb_pl = a.nb_pl;
-  c->match_nb = nb;
-  c->n_qo = nq;  // query-order rows (k_linearize_total) in both modes
+  if (nb == 0) FMX_HIP(hipMemsetAsync(c->m.h_counts.d, 0, (2 * (size_t)c->K + 4) * sizeof(uint32_t), st));
+  c->m.match_nb_pl = a.nb_pl;
+  c->m.match_nb = nb;
+  c->m.n_qo = nq;  // query-order rows (k_linearize_total) in both modes
   // Pair-major correspondences: the counts, offsets and chunk table come from the match
   // kernel's last block (tiled) or from the scan + k_pair_base (wider windows) right
   // away; the row scatter itself may be deferred (defer_scatter: fmx_match, whose
   // caller may only read the query-order outputs) until run_pair_scatter.
-  c->ps = PairScatter{a.nb_pl, nb_pt, a.ntl_pl, a.ntl_pt, a.K, a.tiles, (uint32_t)(thist_cur - c->thist.p),
+  c->m.ps = PairScatter{a.nb_pl, nb_pt, a.ntl_pl, a.ntl_pt, a.K, a.tiles, (uint32_t)(thist_cur - c->m.thist.p),
                       a.prof_work};
-  c->scatter_pending = false;
+  c->m.scatter_pending = false;
   if (sorted && !a.tiles) {
     ProfScope ps(c->prof, PROF_PAIR_SORT, 0.0, st);
     const size_t nh = (size_t)a.K * nb;
     c->scan_scratch.ensure(scan_scratch_size(nh) + 4);
     c->dev_u32.ensure(8);
-    if (nh > 0) exclusive_scan(HistIn{c->hist.p}, HistOut{c->hist_off.p}, nh, c->scan_scratch.p, c->dev_u32.p + 5, st);
+    if (nh > 0) exclusive_scan(HistIn{c->m.hist.p}, HistOut{c->m.hist_off.p}, nh, c->scan_scratch.p, c->dev_u32.p + 5, st);
     else FMX_HIP(hipMemsetAsync(c->dev_u32.p + 5, 0, 4, st));
-    hipLaunchKernelGGL(k_pair_base, dim3(1), dim3(1024), 0, st, a.K, a.nb_pl, nb_pt, c->hist_off.p, c->dev_u32.p + 5,
-                       c->pair_counts.p, c->pair_base.p, c->chunk_range.p, c->chunks.p, c->n_chunks.p,
-                       c->h_counts.d);
+    hipLaunchKernelGGL(k_pair_base, dim3(1), dim3(1024), 0, st, a.K, a.nb_pl, nb_pt, c->m.hist_off.p, c->dev_u32.p + 5,
+                       c->m.pair_counts.p, c->m.pair_base.p, c->m.chunk_range.p, c->m.chunks.p, c->m.n_chunks.p,
+                       c->m.h_counts.d);
     FMX_HIP(hipGetLastError());
   } else if (sorted && nb == 0) {  // no launch: an empty chunk table
-    FMX_HIP(hipMemsetAsync(c->n_chunks.p, 0, sizeof(uint32_t), st));
-    FMX_HIP(hipMemsetAsync(c->chunk_range.p, 0, (size_t)(a.K + 1) * sizeof(uint32_t), st));
+    FMX_HIP(hipMemsetAsync(c->m.n_chunks.p, 0, sizeof(uint32_t), st));
+    FMX_HIP(hipMemsetAsync(c->m.chunk_range.p, 0, (size_t)(a.K + 1) * sizeof(uint32_t), st));
   }
   if (sorted) {
-    c->scatter_pending = true;
+    c->m.scatter_pending = true;
     if (!defer_scatter) run_pair_scatter(c);
   }
   // per-pair counts reach pinned host memory from k_pair_base; consumed at the next sync
-  c->work_copied = c->prof.on;
+  c->m.work_copied = c->prof.on;
   if (c->prof.on) {  // per-block work counters, only needed for the profile's byte model
-    c->h_work.ensure(kWorkWords * (size_t)nb + 8);
+    c->m.h_work.ensure(kWorkWords * (size_t)nb + 8);
     if (nb)
-      FMX_HIP(hipMemcpyAsync(c->h_work.p, c->work.p, kWorkWords * (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      FMX_HIP(hipMemcpyAsync(c->m.h_work.p, c->m.work.p, kWorkWords * (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   }
-  c->counts_pending = true;
-  c->have_match = true;
-  c->have_corr = sorted;  // pair-major correspondences for fmx_linearize
-  c->have_qo = true;      // query-order correspondences for register_scan
+  c->m.counts_pending = true;
+  c->m.have_match = true;
+  c->m.have_corr = sorted;  // pair-major correspondences for fmx_linearize
+  c->m.have_qo = true;      // query-order correspondences for register_scan
 }
 
 // The match at pose_j fused with its single-pose linearization (k_match<.., FUSED>):
@@ -3063,8 +3063,8 @@ void run_match_linearize(fmx_ctx* c, const double* pose_j34, double max_dist, do
   {
     auto kern = dense ? k_match<true, true> : k_match<false, true>;
     hipLaunchKernelGGL(kern, dim3(nb), dim3(kMatchThreads),
-                       std::max<int>(a.K, 1) * sizeof(uint32_t), st, a, view(0), view(1), c->q_pl_pos.p,
-                       c->q_pt_pos.p, c->map_inv_p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->fz_work.p,
+                       std::max<int>(a.K, 1) * sizeof(uint32_t), st, a, view(0), view(1), c->q.pl_pos.p,
+                       c->q.pt_pos.p, c->map_inv_p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->fz_work.p,
                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, so, fz);
     FMX_HIP(hipGetLastError());
   }
@@ -3092,51 +3092,51 @@ void work_fetch(fmx_ctx* c) {
     tc += c->fz_h_work.p[kWorkWords * b + 1];
   }
   match_diag_add(c->fz_h_work.p, c->fz_work_blocks);
-  c->last_probes = tp;
-  c->last_cands = tc;
+  c->m.last_probes = tp;
+  c->m.last_cands = tc;
   c->fz_work_pending = false;
 }
 
 // Consume the asynchronously copied match counts (caller has synchronized or will).
 void match_counts_fetch(fmx_ctx* c, bool wait) {
-  if (!c->counts_pending) return;
+  if (!c->m.counts_pending) return;
   // kTilesScatter: the counts come from the pair scatter's meta block
-  if (c->scatter_pending && c->ps.tiles == kTilesScatter) {
+  if (c->m.scatter_pending && c->m.ps.tiles == kTilesScatter) {
     run_pair_scatter(c);
     wait = true;
   }
   if (wait) stream_wait(c);
   const int K = std::max<int>((int)c->K, 1);
-  c->cnt_pl.assign(c->h_counts.p, c->h_counts.p + c->K);
-  c->cnt_pt.assign(c->h_counts.p + c->K, c->h_counts.p + 2 * c->K);
-  c->ins_tot[0] = c->h_counts.p[2 * c->K];
-  c->ins_tot[1] = c->h_counts.p[2 * c->K + 1];
-  c->cert_tot[0] = c->h_counts.p[2 * c->K + 2];
-  c->cert_tot[1] = c->h_counts.p[2 * c->K + 3];
-  c->rows_pl = c->rows_pt = 0;
+  c->m.cnt_pl.assign(c->m.h_counts.p, c->m.h_counts.p + c->K);
+  c->m.cnt_pt.assign(c->m.h_counts.p + c->K, c->m.h_counts.p + 2 * c->K);
+  c->m.ins_tot[0] = c->m.h_counts.p[2 * c->K];
+  c->m.ins_tot[1] = c->m.h_counts.p[2 * c->K + 1];
+  c->m.cert_tot[0] = c->m.h_counts.p[2 * c->K + 2];
+  c->m.cert_tot[1] = c->m.h_counts.p[2 * c->K + 3];
+  c->m.rows_pl = c->m.rows_pt = 0;
   for (uint32_t k = 0; k < c->K; ++k) {
-    c->rows_pl += c->cnt_pl[k];
-    c->rows_pt += c->cnt_pt[k];
+    c->m.rows_pl += c->m.cnt_pl[k];
+    c->m.rows_pt += c->m.cnt_pt[k];
   }
   (void)K;
-  if (c->work_copied) {  // (a match made before profiling was switched on has none)
+  if (c->m.work_copied) {  // (a match made before profiling was switched on has none)
     double tp = 0, tc = 0;
-    for (uint32_t b = 0; b < c->work_blocks; ++b) {
-      tp += c->h_work.p[kWorkWords * b];
-      tc += c->h_work.p[kWorkWords * b + 1];
+    for (uint32_t b = 0; b < c->m.work_blocks; ++b) {
+      tp += c->m.h_work.p[kWorkWords * b];
+      tc += c->m.h_work.p[kWorkWords * b + 1];
     }
-    match_diag_add(c->h_work.p, c->work_blocks);
-    c->last_probes = tp;
-    c->last_cands = tc;
+    match_diag_add(c->m.h_work.p, c->m.work_blocks);
+    c->m.last_probes = tp;
+    c->m.last_cands = tc;
   }
-  c->counts_pending = false;
+  c->m.counts_pending = false;
 }
 
 void run_insert(fmx_ctx* c, uint64_t scan, uint32_t* n_inserted) {
-  if (!c->have_match) throw StatusError(FMX_E_STATE, "no match to insert from");
+  if (!c->m.have_match) throw StatusError(FMX_E_STATE, "no match to insert from");
   hipStream_t st = c->stream;
   match_counts_fetch(c);  // insert totals of the last match (no wait if already fetched)
-  const uint32_t tot[2] = {c->ins_tot[0], c->ins_tot[1]};
+  const uint32_t tot[2] = {c->m.ins_tot[0], c->m.ins_tot[1]};
   for (int t = 0; t < 2; ++t) {
     const uint32_t nq = t == 0 ? c->n_qpl : c->n_qpt;
     if (tot[t] > nq) throw StatusError(FMX_E_HIP, "implausible insert total");
@@ -3145,18 +3145,18 @@ void run_insert(fmx_ctx* c, uint64_t scan, uint32_t* n_inserted) {
   InsArgs ia;
   ia.nq_pl = c->n_qpl;
   ia.nq_pt = c->n_qpt;
-  ia.nb_pl = c->match_nb_pl;
-  ia.ins = c->m_ins.p;
-  ia.ins_off = c->ins_off.p;
-  ia.q_pl = c->q_pl_pos.p;
-  ia.q_pl_nrm = c->q_pl_nrm.p;
-  ia.q_pt = c->q_pt_pos.p;
+  ia.nb_pl = c->m.match_nb_pl;
+  ia.ins = c->m.m_ins.p;
+  ia.ins_off = c->m.ins_off.p;
+  ia.q_pl = c->q.pl_pos.p;
+  ia.q_pl_nrm = c->q.pl_nrm.p;
+  ia.q_pt = c->q.pt_pos.p;
   ia.d_pl_pos = c->pool[0].pos.p + c->pool[0].used;
   ia.d_pl_nrm = c->pool[0].nrm.p + c->pool[0].used;
   ia.d_pt_pos = c->pool[1].pos.p + c->pool[1].used;
-  if (c->match_nb > 0) {
+  if (c->m.match_nb > 0) {
     ProfScope ps(c->prof, PROF_INSERT, 33.0 * c->n_qpl + 17.0 * c->n_qpt, st);
-    hipLaunchKernelGGL(k_insert, dim3(c->match_nb), dim3(kQPB), 0, st, ia);
+    hipLaunchKernelGGL(k_insert, dim3(c->m.match_nb), dim3(kQPB), 0, st, ia);
     FMX_HIP(hipGetLastError());
   }
   for (int t = 0; t < 2; ++t) {

@@ -689,12 +689,12 @@ namespace {
 void win_persist(fmx_ctx* c, uint64_t j) {
   WinStore& W = c->win;
   hipStream_t st = c->stream;
-  if (!c->have_corr) throw StatusError(FMX_E_STATE, "win_persist: no sorted match");
+  if (!c->m.have_corr) throw StatusError(FMX_E_STATE, "win_persist: no sorted match");
   run_pair_scatter(c);
   uint64_t npl = 0, npt = 0;
   for (uint32_t k = 0; k < c->K; ++k) {
-    npl += c->cnt_pl[k];
-    npt += c->cnt_pt[k];
+    npl += c->m.cnt_pl[k];
+    npt += c->m.cnt_pt[k];
   }
   win_reserve(c, npl, npt);
   WinSeg s;
@@ -704,12 +704,12 @@ void win_persist(fmx_ctx* c, uint64_t j) {
   s.pt_n = (uint32_t)npt;
   uint64_t op = 0, ot = 0;
   for (uint32_t k = 0; k < c->K; ++k) {
-    if (c->cnt_pl[k] + c->cnt_pt[k] > 0)
-      s.pairs.push_back(WinPair{c->map_scans[k], j, s.pl_off + op, s.pt_off + ot, c->cnt_pl[k], c->cnt_pt[k]});
-    op += c->cnt_pl[k];
-    ot += c->cnt_pt[k];
+    if (c->m.cnt_pl[k] + c->m.cnt_pt[k] > 0)
+      s.pairs.push_back(WinPair{c->map_scans[k], j, s.pl_off + op, s.pt_off + ot, c->m.cnt_pl[k], c->m.cnt_pt[k]});
+    op += c->m.cnt_pl[k];
+    ot += c->m.cnt_pt[k];
   }
-  rows_copy(st, c->c_pl.p, c->ld_pl, 0, W.pl[W.cur].p, W.cap_pl, s.pl_off, (uint32_t)npl, c->c_pt.p, c->ld_pt, 0,
+  rows_copy(st, c->m.c_pl.p, c->m.ld_pl, 0, W.pl[W.cur].p, W.cap_pl, s.pl_off, (uint32_t)npl, c->m.c_pt.p, c->m.ld_pt, 0,
             W.pt[W.cur].p, W.cap_pt, s.pt_off, (uint32_t)npt);
   W.tail_pl += npl;
   W.tail_pt += npt;
@@ -822,14 +822,13 @@ void win_set_pairs(fmx_ctx* c, const std::vector<WinPair>& prs, const std::vecto
   // one upload: [chunks (4 words each)][chunk_range]; the pinned staging buffer is
   // reused only after the previous upload's event (no stream synchronization)
   const size_t words = 4 * nch + cr.size();
-  if (W.meta_ev_pending) FMX_HIP(hipEventSynchronize(W.meta_ev));
+  if (W.meta_ev_pending) FMX_HIP(hipEventSynchronize(W.meta_ev.e));
   W.meta.ensure(words + 4);
   W.hmeta.ensure(words + 4);
   std::memcpy(W.hmeta.p, ch.data(), nch * sizeof(Chunk));
   std::memcpy(W.hmeta.p + 4 * nch, cr.data(), cr.size() * sizeof(uint32_t));
   FMX_HIP(hipMemcpyAsync(W.meta.p, W.hmeta.p, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  if (!W.meta_ev) FMX_HIP(hipEventCreateWithFlags(&W.meta_ev, hipEventDisableTiming));
-  FMX_HIP(hipEventRecord(W.meta_ev, st));
+  FMX_HIP(hipEventRecord(W.meta_ev.get(), st));
   W.meta_ev_pending = true;
   W.chunks_p = reinterpret_cast<const Chunk*>(W.meta.p);
   W.chunk_range_p = W.meta.p + 4 * nch;
@@ -868,22 +867,22 @@ void win_linearize_stored(fmx_ctx* c, const double* poses, int nposes, double si
 // already seen complete (the LM's trial linearizations, whose rows the LM's first
 // linearization on the context stream read before them).
 void win_linearize_current(fmx_ctx* c, const double* poses, double sigma, double* G_out, hipStream_t st) {
-  if (!c->have_corr) throw StatusError(FMX_E_STATE, "win_linearize_current: no sorted match");
-  if (c->scatter_pending) st = nullptr;  // its rows are still to be written on the context stream
+  if (!c->m.have_corr) throw StatusError(FMX_E_STATE, "win_linearize_current: no sorted match");
+  if (c->m.scatter_pending) st = nullptr;  // its rows are still to be written on the context stream
   run_pair_scatter(c);
   WinArgs a{};
-  a.chunks = c->chunks.p;
-  a.n_chunks = c->n_chunks.p;
-  a.chunk_range = c->chunk_range.p;
+  a.chunks = c->m.chunks.p;
+  a.n_chunks = c->m.n_chunks.p;
+  a.chunk_range = c->m.chunk_range.p;
   a.npairs = (int)c->K;
-  a.c_pl = c->c_pl.p;
-  a.ld_pl = c->ld_pl;
-  a.c_pt = c->c_pt.p;
-  a.ld_pt = c->ld_pt;
+  a.c_pl = c->m.c_pl.p;
+  a.ld_pl = c->m.ld_pl;
+  a.c_pt = c->m.c_pt.p;
+  a.ld_pt = c->m.ld_pt;
   a.implicit_j = (int)c->K;
   a.inv = 1.0 / sigma;
   // exact row counts arrive with the match counts; the byte model uses the last known
-  win_start(c, a, c->max_chunks, poses, (int)c->K + 1, 72.0 * c->rows_pl + 48.0 * c->rows_pt + 8.0 * kWinG * c->K,
+  win_start(c, a, c->m.max_chunks, poses, (int)c->K + 1, 72.0 * c->m.rows_pl + 48.0 * c->m.rows_pt + 8.0 * kWinG * c->K,
             nullptr, false, st);
   if (G_out) win_finish(c, G_out);
 }
@@ -893,21 +892,21 @@ void win_linearize_current(fmx_ctx* c, const double* poses, double sigma, double
 // (null: launch only, win_finish(c, out) later) = K x 272 doubles, per pair the packed
 // upper 16 x 16 plane moments then the point moments.
 void win_moments_current(fmx_ctx* c, const double* poses, double* out) {
-  if (!c->have_corr) throw StatusError(FMX_E_STATE, "win_moments_current: no sorted match");
+  if (!c->m.have_corr) throw StatusError(FMX_E_STATE, "win_moments_current: no sorted match");
   run_pair_scatter(c);
   WinArgs a{};
-  a.chunks = c->chunks.p;
-  a.n_chunks = c->n_chunks.p;
-  a.chunk_range = c->chunk_range.p;
+  a.chunks = c->m.chunks.p;
+  a.n_chunks = c->m.n_chunks.p;
+  a.chunk_range = c->m.chunk_range.p;
   a.npairs = (int)c->K;
-  a.c_pl = c->c_pl.p;
-  a.ld_pl = c->ld_pl;
-  a.c_pt = c->c_pt.p;
-  a.ld_pt = c->ld_pt;
+  a.c_pl = c->m.c_pl.p;
+  a.ld_pl = c->m.ld_pl;
+  a.c_pt = c->m.c_pt.p;
+  a.ld_pt = c->m.ld_pt;
   a.implicit_j = (int)c->K;
   a.inv = 1.0;
   // bytes: rows read (72 B per plane row, 48 B per point pair) + 2 x 136 doubles per pair
-  win_start(c, a, c->max_chunks, poses, (int)c->K + 1, 72.0 * c->rows_pl + 48.0 * c->rows_pt + 8.0 * 2 * kMomP * c->K,
+  win_start(c, a, c->m.max_chunks, poses, (int)c->K + 1, 72.0 * c->m.rows_pl + 48.0 * c->m.rows_pt + 8.0 * 2 * kMomP * c->K,
             nullptr, true);
   if (out) win_finish(c, out);
 }
@@ -916,7 +915,7 @@ void win_moments_current(fmx_ctx* c, const double* poses, double* out) {
 // pair k at the reference poses poses_i[k], poses_j[k] (the GTSAM seam's "linearize once,
 // evaluate anywhere" form; fmx_moments_contract).  out: K x 272.
 void win_moments_pairs(fmx_ctx* c, const double* poses_i, const double* poses_j, double* out) {
-  if (!c->have_corr) throw StatusError(FMX_E_STATE, "no correspondences (call fmx_match or fmx_corr_set)");
+  if (!c->m.have_corr) throw StatusError(FMX_E_STATE, "no correspondences (call fmx_match or fmx_corr_set)");
   run_pair_scatter(c);
   const int K = (int)c->K;
   if (K == 0) return;
@@ -929,21 +928,21 @@ void win_moments_pairs(fmx_ctx* c, const double* poses_i, const double* poses_j,
     std::memcpy(&table[24 * (size_t)k], poses_i + 12 * (size_t)k, 12 * sizeof(double));
     std::memcpy(&table[24 * (size_t)k + 12], poses_j + 12 * (size_t)k, 12 * sizeof(double));
   }
-  if (c->counts_pending) match_counts_fetch(c);
+  if (c->m.counts_pending) match_counts_fetch(c);
   W.hM.ensure((size_t)K * 2 * kMomP);
   std::memset(W.hM.p, 0, (size_t)K * 2 * kMomP * sizeof(double));  // pairs without rows are never written
   WinArgs a{};
-  a.chunks = c->chunks.p;
-  a.n_chunks = c->n_chunks.p;
-  a.chunk_range = c->chunk_range.p;
+  a.chunks = c->m.chunks.p;
+  a.n_chunks = c->m.n_chunks.p;
+  a.chunk_range = c->m.chunk_range.p;
   a.npairs = K;
-  a.c_pl = c->c_pl.p;
-  a.ld_pl = c->ld_pl;
-  a.c_pt = c->c_pt.p;
-  a.ld_pt = c->ld_pt;
+  a.c_pl = c->m.c_pl.p;
+  a.ld_pl = c->m.ld_pl;
+  a.c_pt = c->m.c_pt.p;
+  a.ld_pt = c->m.ld_pt;
   a.implicit_j = kPairedPoses;
   a.inv = 1.0;
-  win_start(c, a, c->max_chunks, table.data(), 2 * K, 72.0 * c->rows_pl + 48.0 * c->rows_pt + 8.0 * 2 * kMomP * K,
+  win_start(c, a, c->m.max_chunks, table.data(), 2 * K, 72.0 * c->m.rows_pl + 48.0 * c->m.rows_pt + 8.0 * 2 * kMomP * K,
             nullptr, true);
   win_finish(c, out);
 }
@@ -958,7 +957,7 @@ void win_moments_pairs(fmx_ctx* c, const double* poses_i, const double* poses_j,
 // without rows linearize to zero.
 void win_linearize_pairs(fmx_ctx* c, const double* poses_i, const double* poses_j, double sigma, int mode,
                          double* G_out, double* err_out) {
-  if (!c->have_corr) throw StatusError(FMX_E_STATE, "no correspondences (call fmx_match or fmx_corr_set)");
+  if (!c->m.have_corr) throw StatusError(FMX_E_STATE, "no correspondences (call fmx_match or fmx_corr_set)");
   comm_check(c);
   run_pair_scatter(c);  // fmx_match deferred it
   const int K = (int)c->K;
@@ -971,7 +970,7 @@ void win_linearize_pairs(fmx_ctx* c, const double* poses_i, const double* poses_
     std::memcpy(&table[24 * (size_t)k], poses_i + 12 * (size_t)k, 12 * sizeof(double));
     std::memcpy(&table[24 * (size_t)k + 12], poses_j + 12 * (size_t)k, 12 * sizeof(double));
   }
-  if (c->counts_pending) match_counts_fetch(c);  // exact byte model (rows per type)
+  if (c->m.counts_pending) match_counts_fetch(c);  // exact byte model (rows per type)
   W.hG.ensure((size_t)K * kWinG);
   // pairs without rows are never written: zero them first (sharded: in the device
   // buffer the ranks all-reduce, on the stream ahead of the kernel)
@@ -983,17 +982,17 @@ void win_linearize_pairs(fmx_ctx* c, const double* poses_i, const double* poses_
     std::memset(W.hG.p, 0, (size_t)K * kWinG * sizeof(double));
   }
   WinArgs a{};
-  a.chunks = c->chunks.p;
-  a.n_chunks = c->n_chunks.p;
-  a.chunk_range = c->chunk_range.p;
+  a.chunks = c->m.chunks.p;
+  a.n_chunks = c->m.n_chunks.p;
+  a.chunk_range = c->m.chunk_range.p;
   a.npairs = K;
-  a.c_pl = c->c_pl.p;
-  a.ld_pl = c->ld_pl;
-  a.c_pt = c->c_pt.p;
-  a.ld_pt = c->ld_pt;
+  a.c_pl = c->m.c_pl.p;
+  a.ld_pl = c->m.ld_pl;
+  a.c_pt = c->m.c_pt.p;
+  a.ld_pt = c->m.ld_pt;
   a.implicit_j = kPairedPoses;
   a.inv = 1.0 / sigma;  // FastIsotropic invsigma_ (gtsam.hpp:96)
-  win_start(c, a, c->max_chunks, table.data(), 2 * K, 72.0 * c->rows_pl + 48.0 * c->rows_pt + 8.0 * kWinG * K,
+  win_start(c, a, c->m.max_chunks, table.data(), 2 * K, 72.0 * c->m.rows_pl + 48.0 * c->m.rows_pt + 8.0 * kWinG * K,
             comm ? c->d_sum.p : nullptr);
   if (comm) {  // every pair's G (and error) summed over the ranks on this stream
     comm_allreduce_publish(c, c->d_sum.p, (size_t)K * kWinG, W.hG);
