@@ -29,12 +29,8 @@ namespace fmx {
 // ~2 probes and ~2 candidates per query): they run in many waves of blocks, so more
 // queries per wave raise the loads in flight.  C5 match per launch: 4 lanes 0.55 ms,
 // 2 lanes 0.40, 1 lane 0.245 (C4: 8 lanes 0.22 vs 4 lanes 0.28 ms per scan).
-#ifndef FMX_MATCH_LARGE_MIN
-#define FMX_MATCH_LARGE_MIN (128u << 10)  // queries from which the large-set build (fmx::gl) is used
-#endif
-int match_group_for(uint64_t nq, uint32_t K) {
-  return nq >= (uint64_t)(FMX_MATCH_LARGE_MIN) && K <= kMatchTileMaxPairs ? 1 : 8;
-}
+// The threshold (FMX_MATCH_LARGE_MIN) and the choice itself: pair_sort_plan.hpp.
+int match_group_for(uint64_t nq, uint32_t K) { return (int)match_group(nq, K); }
 void run_map_build(fmx_ctx* c, const std::vector<uint64_t>& scans, const double* poses34, double w, hipStream_t st) {
   ++c->warm_gen;  // a new map: no warm start from an earlier match
   g8::run_map_build(c, scans, poses34, w, st);  // the same build in both variants
@@ -1883,6 +1879,74 @@ fmx_status fmx_corr_set(fmx_ctx* c, uint32_t K, const uint32_t* np, const double
     ++c->corr_gen;
     upload_corr(c, K, np, ppi, pni, ppj, nt, tpi, tpj);
   });
+}
+
+fmx_status fmx_corr_download(fmx_ctx* c, uint32_t sizes[4], uint32_t* counts, uint32_t* pair_base,
+                             uint32_t* chunk_range, uint32_t cap_pairs, uint32_t* chunks, uint32_t cap_chunks,
+                             double* ppi, double* pni, double* ppj, uint32_t cap_plane, double* tpi, double* tpj,
+                             uint32_t cap_point) {
+  return guard(c, [&] {  // (guard: a deferred match is launched first)
+    if (!c->m.have_corr) throw StatusError(FMX_E_STATE, "no correspondences (call fmx_match or fmx_corr_set)");
+    run_pair_scatter(c);  // fmx_match deferred it
+    FMX_HIP(hipStreamSynchronize(c->stream));
+    const uint32_t K = c->K;
+    // a match without queries launched nothing: its tables are empty, not the device's stale words
+    const bool empty = c->m.have_match && c->m.match_nb == 0;
+    std::vector<uint32_t> cnt(2 * (size_t)K + 1, 0u), base(2 * (size_t)K + 1, 0u), cr((size_t)K + 1, 0u);
+    uint32_t nch = 0;
+    if (K && !empty) {
+      FMX_HIP(hipMemcpy(cnt.data(), c->m.pair_counts.p, 2 * (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      FMX_HIP(hipMemcpy(base.data(), c->m.pair_base.p, 2 * (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      FMX_HIP(hipMemcpy(cr.data(), c->m.chunk_range.p, ((size_t)K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      FMX_HIP(hipMemcpy(&nch, c->m.n_chunks.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    uint64_t Np = 0, Nt = 0;
+    for (uint32_t k = 0; k < K; ++k) {
+      Np += cnt[k];
+      Nt += cnt[K + k];
+    }
+    // the device's own words size the copies below: refuse what cannot be true
+    if (Np + 1 > c->m.ld_pl || Nt + 1 > c->m.ld_pt || nch > c->m.chunks.cap)
+      throw StatusError(FMX_E_HIP, "implausible correspondence tables");
+    if (((counts || pair_base || chunk_range) && cap_pairs < K) || (chunks && cap_chunks < nch) ||
+        ((ppi || pni || ppj) && cap_plane < Np) || ((tpi || tpj) && cap_point < Nt))
+      throw StatusError(FMX_E_INVAL, "fmx_corr_download: capacity too small");
+    if (sizes) {
+      sizes[0] = K;
+      sizes[1] = nch;
+      sizes[2] = (uint32_t)Np;
+      sizes[3] = (uint32_t)Nt;
+    }
+    if (counts) std::memcpy(counts, cnt.data(), 2 * (size_t)K * sizeof(uint32_t));
+    if (pair_base) std::memcpy(pair_base, base.data(), 2 * (size_t)K * sizeof(uint32_t));
+    if (chunk_range) std::memcpy(chunk_range, cr.data(), ((size_t)K + 1) * sizeof(uint32_t));
+    if (chunks && nch) FMX_HIP(hipMemcpy(chunks, c->m.chunks.p, (size_t)nch * sizeof(Chunk), hipMemcpyDeviceToHost));
+    // field f of row r: [f][ld] on the device, [r][3] per field on the host
+    auto rows = [&](const double* dev, size_t ld, uint64_t n, int field, double* out) {
+      if (!out || n == 0) return;
+      std::vector<double> h(3 * (size_t)n);
+      for (int d = 0; d < 3; ++d)
+        FMX_HIP(hipMemcpy(h.data() + (size_t)d * n, dev + (size_t)(3 * field + d) * ld, n * sizeof(double),
+                          hipMemcpyDeviceToHost));
+      for (uint64_t r = 0; r < n; ++r)
+        for (int d = 0; d < 3; ++d) out[3 * r + d] = h[(size_t)d * n + r];
+    };
+    rows(c->m.c_pl.p, c->m.ld_pl, Np, 0, ppi);
+    rows(c->m.c_pl.p, c->m.ld_pl, Np, 1, pni);
+    rows(c->m.c_pl.p, c->m.ld_pl, Np, 2, ppj);
+    rows(c->m.c_pt.p, c->m.ld_pt, Nt, 0, tpi);
+    rows(c->m.c_pt.p, c->m.ld_pt, Nt, 1, tpj);
+  });
+}
+
+fmx_status fmx_pair_sort_plan(uint32_t n_planar, uint32_t n_point, uint32_t K, int sorted, uint32_t out[8]) {
+  if (!out) return FMX_E_INVAL;
+  const PairSortPlan p = pair_sort_plan(n_planar, n_point, K, sorted != 0);
+  if (p.hist_words > 0xFFFFFFFFull) return FMX_E_INVAL;
+  const uint32_t v[8] = {p.group, (uint32_t)p.form, p.nb_pl, p.nb_pt, p.ntl_pl, p.ntl_pt, (uint32_t)p.hist_words,
+                         p.scan_launches};
+  std::memcpy(out, v, sizeof(v));
+  return FMX_OK;
 }
 
 fmx_status fmx_linearize(fmx_ctx* c, const double* pi, const double* pj, double sigma, int single, double* G,

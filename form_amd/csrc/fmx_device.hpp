@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pair_sort_plan.hpp"
+
 namespace fmx {
 
 constexpr int kWave = 64;
@@ -128,6 +130,7 @@ __device__ __forceinline__ void publish_flag(uint32_t* flag, uint32_t seq) {
 constexpr int kScanThreads = 1024;
 constexpr int kScanItems = 4;
 constexpr int kScanTile = kScanThreads * kScanItems;
+static_assert((size_t)kScanTile == kScanTileWords, "pair_sort_plan.hpp counts scan launches by this tile");
 
 template <class In>
 __global__ __launch_bounds__(kScanThreads) void k_scan_reduce(In in, size_t n, uint32_t* bsum) {
@@ -202,7 +205,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_tiles(In in, Out out, siz
 
 // One workgroup scans the whole array tile by tile (coalesced, carry in LDS): one
 // launch instead of three, for arrays up to kScanSingleMax.
-constexpr size_t kScanSingleMax = (size_t)kScanTile * 4;
+constexpr size_t kScanSingleMax = kScanSingleMaxWords;  // pair_sort_plan.hpp
 template <class In, class Out>
 __global__ __launch_bounds__(kScanThreads) void k_scan_single(In in, Out out, size_t n, uint32_t* total) {
   __shared__ uint32_t ws[kScanThreads / kWave];

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "fmx/fmx.h"
+#include "pair_sort_plan.hpp"
 #include "stage.hpp"
 
 namespace fmx {
@@ -884,10 +885,7 @@ inline uint32_t next_flag(fmx_ctx* c) {
   void run_match_linearize(fmx_ctx* c, const double* pose_j34, double max_dist, double sigma, double* dst, \
                            uint32_t* flag, uint32_t seq);                                              \
   void work_fetch(fmx_ctx* c);
-// Windows of at most this many map scans (pairs) use the tiled pair sort; wider ones a
-// per-match-block histogram whose scatter ranks within one wave, so they take the g8
-// build (32 queries per block) whatever the query count.
-constexpr uint32_t kMatchTileMaxPairs = 256;
+// (kMatchTileMaxPairs, the window width up to which the pair sort is tiled: pair_sort_plan.hpp)
 namespace g8 { FMX_VM_DECLS }
 namespace gl { FMX_VM_DECLS }
 #undef FMX_VM_DECLS

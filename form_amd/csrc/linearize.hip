@@ -211,7 +211,8 @@ void upload_corr(fmx_ctx* c, uint32_t K, const uint32_t* np, const double* ppi, 
   c->m.chunk_range.ensure(K + 1);
   c->m.n_chunks.ensure(1);
   c->m.pair_counts.ensure(2 * (size_t)K + 1);
-  c->h_meta.ensure(4 * (size_t)nch + 2 * (K + 1) + 2 * (size_t)K + 4);
+  c->m.pair_base.ensure(2 * (size_t)K + 1);
+  c->h_meta.ensure(4 * (size_t)nch + 2 * (K + 1) + 4 * (size_t)K + 4);
   uint32_t* hm = c->h_meta.p;
   std::memcpy(hm, ch.data(), nch * sizeof(Chunk));
   std::memcpy(hm + 4 * nch, cr.data(), (K + 1) * sizeof(uint32_t));
@@ -222,6 +223,16 @@ void upload_corr(fmx_ctx* c, uint32_t K, const uint32_t* np, const double* ppi, 
   FMX_HIP(hipMemcpyAsync(c->m.chunk_range.p, hm + 4 * nch, (K + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   FMX_HIP(hipMemcpyAsync(c->m.n_chunks.p, hm + 4 * nch + K + 1, sizeof(uint32_t), hipMemcpyHostToDevice, st));
   FMX_HIP(hipMemcpyAsync(c->m.pair_counts.p, hm + 4 * nch + K + 2, 2 * K * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  // each pair's first row per type, as a sorted match leaves them (fmx_corr_download)
+  uint32_t* hb = hm + 4 * nch + 3 * (size_t)K + 2;
+  uint32_t bp = 0, bt = 0;
+  for (uint32_t k = 0; k < K; ++k) {
+    hb[k] = bp;
+    hb[K + k] = bt;
+    bp += np[k];
+    bt += nt[k];
+  }
+  FMX_HIP(hipMemcpyAsync(c->m.pair_base.p, hb, 2 * K * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   FMX_HIP(hipStreamSynchronize(st));  // staging buffers may be reused after return
   c->m.max_chunks = std::max<uint32_t>(nch, 1);
   c->m.rows_pl = Np;

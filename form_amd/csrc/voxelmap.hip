@@ -598,9 +598,7 @@ constexpr int kMatchThreads = kQPB * kGroup;  // 256
 constexpr int kSmallCell = FMX_SMALL_CELL;  // neighbour cells with at most this many records: one lane folds them
 // Tiled pair sort: a tile = kTileBlocks match blocks of one type = 1024 queries, one
 // k_pair_scatter_t block; the match counts matches per (type, pair, tile).
-#ifndef FMX_TILE_Q
-#define FMX_TILE_Q 1024  // queries per pair-scatter tile (A/B switch)
-#endif
+// (FMX_TILE_Q, queries per pair-scatter tile: pair_sort_plan.hpp)
 constexpr int kTileBlocks = FMX_TILE_Q / kQPB > 0 ? FMX_TILE_Q / kQPB : 1;
 constexpr int kTileQ = kTileBlocks * kQPB;  // 1024
 constexpr int kTileMaxPairs = (int)kMatchTileMaxPairs;  // LDS bound of the tiled path (wider windows: per-block path)
@@ -609,8 +607,9 @@ constexpr int kWorkWords = 8;               // per-block match work / diagnostic
 // (kTilesTail), or every pair-scatter block its own share plus one extra scatter block
 // for the per-pair tables and insert offsets (kTilesScatter: the match has no serial
 // tail; used while the whole count table fits the scatter's LDS, kScatterTab words).
+// pair_sort_plan.hpp chooses (kScatterTab is defined there).
 constexpr int kTilesTail = 1, kTilesScatter = 2;
-constexpr uint32_t kScatterTab = 6144;
+static_assert(kMatchThreads == kMatchBlockThreads, "pair_sort_plan.hpp sizes match blocks by this");
 
 // Outputs of the tiled pair sort's last-block pass (consumed by later launches).
 struct SortOut {
@@ -2853,17 +2852,16 @@ void run_match(fmx_ctx* c, const double* pose_j34, double max_dist, double min_d
   }
   a.nq_pl = c->n_qpl;
   a.nq_pt = c->n_qpt;
-  a.nb_pl = (c->n_qpl + kQPB - 1) / kQPB;
-  const uint32_t nb_pt = (c->n_qpt + kQPB - 1) / kQPB;
+  // blocks, tiles and the form of the pair sort: one host function (pair_sort_plan.hpp)
+  const PairSortPlan plan = pair_sort_plan_group((uint32_t)kGroup, c->n_qpl, c->n_qpt, c->K, sorted);
+  a.nb_pl = plan.nb_pl;
+  const uint32_t nb_pt = plan.nb_pt;
   a.nb_pt = nb_pt;
   a.K = (int)c->K;
   a.sorted = sorted ? 1 : 0;
-  a.ntl_pl = (a.nb_pl + kTileBlocks - 1) / kTileBlocks;
-  a.ntl_pt = (nb_pt + kTileBlocks - 1) / kTileBlocks;
-  // wider windows: per-block histograms; a count table that fits the scatter's LDS: no
-  // match tail (the scatter scans it)
-  const uint64_t tab = (uint64_t)c->K * (a.ntl_pl + a.ntl_pt);
-  a.tiles = !sorted || c->K > (uint32_t)kTileMaxPairs ? 0 : tab <= kScatterTab ? kTilesScatter : kTilesTail;
+  a.ntl_pl = plan.ntl_pl;
+  a.ntl_pt = plan.ntl_pt;
+  a.tiles = plan.form == kPairSortScatter ? kTilesScatter : plan.form == kPairSortTail ? kTilesTail : 0;
   const uint32_t nq = c->n_qpl + c->n_qpt;
   c->m.m_pair.ensure(nq + 1);
   c->m.m_d2.ensure(nq + 1);

@@ -108,7 +108,24 @@ EXPORTED = [
     "fmx_corr_generation", "fmx_moments", "fmx_moments_contract",
     "fmx_deskew_configure", "fmx_deskew_set_twist", "fmx_deskew_last", "fmx_deskew",
     "fmx_organize_configure", "fmx_organize", "fmx_register_cloud", "fmx_deskew_cells",
+    "fmx_corr_download", "fmx_pair_sort_plan",
 ]
+
+PAIR_SORT_FORMS = ("none", "per-block", "tail-scanned", "scatter-scanned")
+
+
+def pair_sort_plan(n_planar: int, n_point: int, K: int, sorted: bool = True) -> dict:
+    """fmx_pair_sort_plan (host only, no context): the form the pair sort of such a match
+    takes (form_amd/csrc/pair_sort_plan.hpp)."""
+    out = np.zeros(8, np.uint32)
+    st = lib().fmx_pair_sort_plan(C.c_uint32(n_planar), C.c_uint32(n_point), C.c_uint32(K), C.c_int(int(sorted)),
+                                  _p(out))
+    if st != FMX_OK:
+        raise FmxError(st, "fmx_pair_sort_plan")
+    keys = ("group", "form", "nb_pl", "nb_pt", "ntl_pl", "ntl_pt", "hist_words", "scan_launches")
+    plan = {k: int(v) for k, v in zip(keys, out)}
+    plan["form"] = PAIR_SORT_FORMS[plan["form"]]
+    return plan
 
 
 def _p(a):
@@ -317,6 +334,28 @@ class Context:
         self._chk(self._L.fmx_corr_set(self.h, C.c_uint32(len(n_plane)), _p(n_plane), _p(arrs[0]), _p(arrs[1]),
                                        _p(arrs[2]), _p(n_point), _p(arrs[3]), _p(arrs[4])))
         self.K = len(n_plane)
+
+    def corr_download(self):
+        """fmx_corr_download: the pair-major correspondences as the device holds them (after
+        a sorted match or corr_set): per-pair counts and first rows per type, the chunk table
+        and the rows in device order."""
+        f = self._L.fmx_corr_download
+        z = C.c_uint32(0)
+        sizes = np.zeros(4, np.uint32)
+        self._chk(f(self.h, _p(sizes), None, None, None, z, None, z, None, None, None, z, None, None, z))
+        K, nch, n_pl, n_pt = (int(v) for v in sizes)
+        counts = np.zeros(2 * K, np.uint32)
+        base = np.zeros(2 * K, np.uint32)
+        chunk_range = np.zeros(K + 1, np.uint32)
+        chunks = np.zeros((nch, 4), np.uint32)
+        pl = [np.zeros((n_pl, 3), np.float64) for _ in range(3)]
+        pt = [np.zeros((n_pt, 3), np.float64) for _ in range(2)]
+        self._chk(f(self.h, _p(sizes), _p(counts), _p(base), _p(chunk_range), C.c_uint32(K), _p(chunks),
+                    C.c_uint32(nch), _p(pl[0]), _p(pl[1]), _p(pl[2]), C.c_uint32(n_pl), _p(pt[0]), _p(pt[1]),
+                    C.c_uint32(n_pt)))
+        return dict(counts_plane=counts[:K], counts_point=counts[K:], base_plane=base[:K], base_point=base[K:],
+                    chunk_range=chunk_range, n_chunks=int(sizes[1]), chunks=chunks, plane_pi=pl[0], plane_ni=pl[1],
+                    plane_pj=pl[2], point_pi=pt[0], point_pj=pt[1])
 
     def linearize(self, poses_i, poses_j, sigma: float = 0.1, single: bool = False):
         pi_ = np.ascontiguousarray(poses_i, np.float64).reshape(-1, 12)

@@ -184,6 +184,33 @@ fmx_status fmx_map_insert(fmx_ctx* ctx, double min_dist_map, uint32_t* n_inserte
 fmx_status fmx_corr_set(fmx_ctx* ctx, uint32_t K, const uint32_t* n_plane,
                         const double* plane_pi, const double* plane_ni, const double* plane_pj,
                         const uint32_t* n_point, const double* point_pi, const double* point_pj);
+/* The inverse of fmx_corr_set: the pair-major correspondences as the device holds them,
+ * after a sorted fmx_match (a deferred match and a deferred row scatter are launched
+ * first, as by every other reader) or after fmx_corr_set; FMX_E_STATE otherwise.  Nothing
+ * is recomputed on the host.  sizes (may be NULL): K, the chunk count, the plane rows and
+ * the point rows.  Every output pointer may be NULL and is then skipped with its
+ * capacity; a call with only `sizes` asks for the capacities the next one needs.
+ *   counts, pair_base  [2K]: per pair the plane rows then the point rows, and each
+ *                      pair's first row per type; needs cap_pairs >= K
+ *   chunk_range        [K + 1] (cap_pairs >= K): pair k owns chunks
+ *                      [chunk_range[k], chunk_range[k + 1])
+ *   chunks             [n_chunks][4] = type (0 plane, 1 point), pair, first row, end row:
+ *                      per pair its plane chunks then its point chunks, 256 rows each;
+ *                      needs cap_chunks >= n_chunks
+ *   plane_* / point_*  the rows in device row order, 3 doubles per field and row as
+ *                      fmx_corr_set takes them; cap_plane / cap_point in rows
+ * A capacity that is too small: FMX_E_INVAL, and nothing is written. */
+fmx_status fmx_corr_download(fmx_ctx* ctx, uint32_t sizes[4], uint32_t* counts, uint32_t* pair_base,
+                             uint32_t* chunk_range, uint32_t cap_pairs, uint32_t* chunks, uint32_t cap_chunks,
+                             double* plane_pi, double* plane_ni, double* plane_pj, uint32_t cap_plane,
+                             double* point_pi, double* point_pj, uint32_t cap_point);
+/* Host only (no context, no device): the form the pair sort of a match of n_planar +
+ * n_point queries against K scans takes (form_amd/csrc/pair_sort_plan.hpp).
+ * out = lanes per query (8 or 1), form (0 not sorted, 1 per-block histograms, 2 counts
+ * scanned by the match's last block, 3 by the pair scatter), match blocks planar / point,
+ * tiles planar / point, words scanned by the per-block form (else 0), scan launches
+ * (0, 1 or 3).  FMX_E_INVAL: null out, or a scanned word count beyond 32 bits. */
+fmx_status fmx_pair_sort_plan(uint32_t n_planar, uint32_t n_point, uint32_t K, int sorted, uint32_t out[8]);
 /* A counter that changes whenever the context's correspondences may have been replaced
  * (fmx_match, fmx_corr_set, fmx_register_scan): a caller caching fmx_linearize results per
  * set of poses (fmx_seam.hpp's FmxBatch) keys its cache on it as well. */
