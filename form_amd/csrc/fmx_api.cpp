@@ -67,7 +67,7 @@ void match_counts_fetch(fmx_ctx* c, bool wait) {
 static const char* kProfNames[PROF_COUNT] = {"extract_rows", "closest",   "fit",       "compact", "map_build",
                                              "match",        "pair_sort", "linearize", "insert",  "window",
                                              "match_linearize", "unpack", "moments", "deskew",
-                                             "organize"};
+                                             "organize", "dense"};
 
 ProfScope::ProfScope(Prof& p, int i, double by, hipStream_t s) : pr(p), id(i), bytes(by), st(s) {
   if (!pr.on) return;
@@ -1356,6 +1356,68 @@ void finish_tail(fmx_ctx* c) {
   if (c->est) finish_tail(c, *c->est);
 }
 
+// ---- dense voxel map (densemap.hip)
+// Exactly n elements (DBuf::ensure doubles what it is asked for: not for a table of up to
+// 2^30 slots); a failed allocation is a capacity error, not a HIP one.
+template <class T>
+void alloc_exact(DBuf<T>& b, size_t n) {
+  b.release();
+  T* p = nullptr;
+  if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) {
+    (void)hipGetLastError();
+    throw StatusError(FMX_E_OOM, "dense map: device allocation of " + std::to_string(n * sizeof(T)) + " bytes failed");
+  }
+  b.p = p;
+  b.cap = n;
+}
+void dense_release(fmx_ctx* c) {
+  auto& D = c->dense;
+  D.on = false;
+  D.keys.release();
+  D.tags.release();
+  D.hits.release();
+  D.xyz.release();
+  D.max_voxels = D.slots = D.voxels = 0;
+  D.seq_scan.clear();
+}
+// Queue the integration of the n device points at d (the capacity rule checked by the
+// caller) on the context stream; returns the completion word's value to wait for, 0 when
+// nothing was launched (n = 0: an integration that counts nothing).
+uint32_t dense_queue(fmx_ctx* c, const float4* d, size_t n, const double* pose34, uint64_t scan_idx) {
+  auto& D = c->dense;
+  D.used = true;
+  uint32_t flag = 0;
+  if (n) {
+    flag = D.flag_seq + 1;
+    run_dense_integrate(c, d, n, pose34, (uint32_t)D.seq_scan.size(), flag, c->stream);
+    D.flag_seq = D.pending = flag;
+  } else {
+    std::memset(D.h_res.p, 0, 5 * sizeof(uint32_t));
+  }
+  D.seq_scan.push_back(scan_idx);
+  return flag;
+}
+// Wait for it (the fill's last block has then seen every block's ticket: the scan is read),
+// take the new voxel total and the counts.
+void dense_finish(fmx_ctx* c, uint32_t flag, fmx_dense_counts* out) {
+  auto& D = c->dense;
+  if (flag) {
+    wait_flag(c, D.h_res.p + 7, flag, c->stream);
+    D.voxels = D.h_res.p[5];
+    D.pending = 0;
+  }
+  if (out) {
+    const uint32_t* h = D.h_res.p;
+    *out = fmx_dense_counts{h[0], h[1], h[2], h[3], h[4]};
+  }
+}
+
+// An integration whose wait never ran (the call that queued it failed in between): its
+// voxel total is taken before anything reads or relies on the host's copy.
+void dense_settle(fmx_ctx* c) {
+  if (c->dense.pending) dense_finish(c, c->dense.pending, nullptr);
+}
+
 // dsk_cells (fmx_register_cloud with deskewing on): the scan's per-cell sweep fractions
 void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feature_counts* out,
                    const float* dsk_cells = nullptr) {
@@ -1383,6 +1445,15 @@ void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feat
                                       " != " + std::to_string(n));
   const uint64_t j = e.init ? e.scan + 1 : 0;
   FMX_TRACE_("scan %llu: register_scan\n", (unsigned long long)j);
+  // Dense map: whether this scan is integrated is known now (the previous integration has
+  // finished, so the voxel total is current); a capacity refusal is reported, never thrown
+  auto& DM = c->dense;
+  dense_settle(c);
+  DM.last = fmx_dense_counts{};
+  DM.last_integrated = 0;
+  const bool dense_go = DM.on && j % DM.every == 0 && DM.voxels + n <= DM.max_voxels;
+  if (DM.on && j % DM.every == 0 && !dense_go) DM.last_integrated = -1;
+  bool took_pf = false;
   const uint64_t waits0 = c->host_waits;
   const uint64_t spec0 = c->spec_launched, hits0 = c->spec_hits, pf0 = c->pf_used;
   c->spec_valid = false;  // a new map and query set: no speculation carries over
@@ -1475,6 +1546,7 @@ void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feat
       // pipelined: the features were extracted during the previous registration.  The
       // first ICP match (at the prediction) is queued before the host's finish() work,
       // which then overlaps it; the ICP loop takes it as a speculative match.
+      took_pf = true;
       if (!host_done) map_inputs();
       FMX_HIP(hipStreamWaitEvent(c->stream, c->ev_join.last(), 0));
       if (!P.disable_smoothing) {
@@ -1497,6 +1569,21 @@ void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feat
   }
   std::memcpy(c->dsk.last, dsk_xi, sizeof(dsk_xi));
   c->dsk.last_src = dsk_src;
+  // Dense map: the scan the extractor saw, on the device.  A host-announced scan's device
+  // copy is overwritten by the next announced scan's DMA during this registration (the
+  // pf_launch offers below, on the side stream): keep a copy, queued ahead of them.
+  const float4* dense_src = nullptr;
+  if (dense_go) {
+    if (c->dsk.on) {
+      dense_src = took_pf ? c->dsk.pf_out.p : c->dsk.out.p;
+    } else if (took_pf && c->pf_host) {
+      DM.keep.ensure(n);  // sized by fmx_dense_configure: no allocation here
+      FMX_HIP(hipMemcpyAsync(DM.keep.p, c->pf_scan.p, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+      dense_src = DM.keep.p;
+    } else {
+      dense_src = on_dev ? reinterpret_cast<const float4*>(xyzw) : c->scan.p;
+    }
+  }
   FMX_HIP(hipStreamWaitEvent(c->stream, c->ev_join.last(), 0));
   FMX_TRACE_("scan %llu: extracted %u + %u, map queued\n", (unsigned long long)j, fc.planar, fc.point);
   HostScope* hs_icp = new HostScope(4);
@@ -1552,6 +1639,11 @@ void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feat
     run_insert(c, j, nullptr);
     keyscan_step(c, e, j, fc.planar + fc.point);  // marginalization: deferred (finish_tail)
   }
+  // Dense map: the scan's pose is final (what fmx_current_pose returns from here on).  Its
+  // two launches go ahead of the announced scan's deskew below, which overwrites the
+  // buffer a pipelined deskewed scan is read from (same stream: ordered).
+  uint32_t dense_flag = 0;
+  if (dense_go) dense_flag = dense_queue(c, dense_src, n, e.values.at(j).m, j);
   if (c->dsk.on && c->ann_ptr && !c->pf_launched) {
     // deskewing: the announced scan's twist needs this scan's final poses and the keyscan
     // step's verdict, both in by now; its deskew + extraction overlap the rest of this
@@ -1559,6 +1651,13 @@ void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feat
     double nxt[6];
     const int src = deskew_next_twist(c, nxt);
     pf_launch(c, true, nxt, src);
+  }
+  if (dense_go) {
+    // the one wait the map adds: for the fill's completion word, not for the stream (the
+    // announced scan's extraction may be queued behind it).  A device-resident caller scan
+    // may be overwritten once this call returns.
+    dense_finish(c, dense_flag, &DM.last);
+    DM.last_integrated = 1;
   }
   FMX_TRACE_("scan %llu: done\n", (unsigned long long)j);
   c->stats[0] = icp;
@@ -2425,6 +2524,159 @@ fmx_status fmx_deskew_cells(fmx_ctx* c, const float* xyzw, size_t n, int src_on_
     run_deskew_cells(c, d_in, d_out, d_fr, n, twist, c->stream);
     if (!dst_on_dev) FMX_HIP(hipMemcpyAsync(out, d_out, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns in / out again
+  });
+}
+
+// ---- dense voxel map (densemap.hip)
+fmx_status fmx_dense_configure(fmx_ctx* c, const fmx_dense_params* p) {
+  return guard<false>(c, [&] {
+    if (!p) throw StatusError(FMX_E_INVAL, "null dense map parameters");
+    auto& D = c->dense;
+    if (c->est || D.used)
+      throw StatusError(FMX_E_STATE, "fmx_dense_configure after the first registration or integration");
+    if (!p->enable) {
+      sync_all(c);
+      dense_release(c);
+      return;
+    }
+    if (!(p->voxel_width > 0.0) || !std::isfinite(p->voxel_width))
+      throw StatusError(FMX_E_INVAL, "dense map: the voxel width must be finite and positive");
+    if (p->max_voxels == 0 || p->max_voxels > (1ull << 29))
+      throw StatusError(FMX_E_INVAL, "dense map: max_voxels must be in [1, 2^29]");
+    double min2 = p->min_norm_squared, max2 = p->max_norm_squared;
+    if (min2 == 0.0 && max2 == 0.0) {
+      min2 = c->P.extraction.min_norm_squared;
+      max2 = c->P.extraction.max_norm_squared;
+    }
+    if (!(min2 >= 0.0) || !(max2 > min2))  // also rejects NaN
+      throw StatusError(FMX_E_INVAL, "dense map: the range gate must satisfy 0 <= min_norm_squared < max_norm_squared");
+    uint64_t slots = 2;
+    while (slots < 2 * p->max_voxels) slots <<= 1;
+    sync_all(c);
+    dense_release(c);
+    try {
+      alloc_exact(D.keys, slots);
+      alloc_exact(D.tags, slots);
+      alloc_exact(D.hits, slots);
+      alloc_exact(D.xyz, 3 * slots);
+    } catch (...) {
+      dense_release(c);
+      throw;
+    }
+    D.voxel_w = p->voxel_width;
+    D.min2 = min2;
+    D.max2 = max2;
+    D.every = p->every ? p->every : 1;
+    D.max_voxels = p->max_voxels;
+    D.slots = slots;
+    D.cnt.ensure(8);
+    D.out_n.ensure(1);
+    D.h_n.ensure(1);
+    D.h_res.ensure(8);
+    std::memset(D.h_res.p, 0, 8 * sizeof(uint32_t));
+    D.flag_seq = D.pending = 0;
+    // every per-scan buffer now: a registration allocates nothing for the map
+    const auto& E = c->P.extraction;
+    const size_t RC = (size_t)(E.num_rows > 0 ? E.num_rows : 0) * (size_t)(E.num_columns > 0 ? E.num_columns : 0);
+    if (RC) {
+      D.slot_of.ensure(RC);
+      D.keep.ensure(RC);
+    }
+    run_dense_clear(c, c->stream);  // on the context stream, which the claims are ordered behind
+    D.on = true;
+  });
+}
+
+fmx_status fmx_dense_integrate(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double pose34[12],
+                               uint64_t scan_idx, fmx_dense_counts* counts) {
+  return guard<false>(c, [&] {
+    auto& D = c->dense;
+    if (!D.on) throw StatusError(FMX_E_STATE, "the dense map is not enabled (fmx_dense_configure)");
+    dense_settle(c);
+    if (!pose34) throw StatusError(FMX_E_INVAL, "null pose");
+    for (int k = 0; k < 12; ++k)
+      if (!std::isfinite(pose34[k])) throw StatusError(FMX_E_INVAL, "non-finite pose");
+    if ((unsigned long long)n >= (1ull << 32)) throw StatusError(FMX_E_INVAL, "an integration holds fewer than 2^32 points");
+    if (n && !xyzw) throw StatusError(FMX_E_INVAL, "null points");
+    if (D.voxels + n > D.max_voxels)
+      throw StatusError(FMX_E_OOM, "dense map: " + std::to_string(D.voxels) + " voxels + " + std::to_string(n) +
+                                       " points exceed max_voxels " + std::to_string(D.max_voxels));
+    if (D.seq_scan.size() >= 0xFFFFFFFEull) throw StatusError(FMX_E_STATE, "dense map: integration counter exhausted");
+    const float4* d = reinterpret_cast<const float4*>(xyzw);
+    if (n && !src_on_dev) {
+      D.in.ensure(n);
+      FMX_HIP(hipMemcpyAsync(D.in.p, xyzw, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+      d = D.in.p;
+    }
+    const uint32_t flag = dense_queue(c, d, n, pose34, scan_idx);
+    dense_finish(c, flag, counts);  // the caller owns the points again
+  });
+}
+
+fmx_status fmx_dense_last(fmx_ctx* c, fmx_dense_counts* counts, int* integrated) {
+  return guard<false>(c, [&] {
+    if (counts) *counts = c->dense.last;
+    if (integrated) *integrated = c->dense.last_integrated;
+  });
+}
+
+fmx_status fmx_dense_stats(fmx_ctx* c, uint64_t out[4]) {
+  return guard<false>(c, [&] {
+    if (!out) throw StatusError(FMX_E_INVAL, "null output");
+    dense_settle(c);
+    const auto& D = c->dense;
+    out[0] = D.voxels;
+    out[1] = D.max_voxels;
+    out[2] = D.seq_scan.size();
+    out[3] = D.slots;
+  });
+}
+
+fmx_status fmx_dense_download(fmx_ctx* c, uint32_t min_hits, double* xyz, uint64_t* scan, uint32_t* index,
+                              uint32_t* hits, uint32_t* n) {
+  return guard<false>(c, [&] {
+    auto& D = c->dense;
+    if (!D.on) throw StatusError(FMX_E_STATE, "the dense map is not enabled (fmx_dense_configure)");
+    dense_settle(c);
+    if (!n) throw StatusError(FMX_E_INVAL, "null count");
+    const uint32_t mh = min_hits ? min_hits : 1;
+    const uint32_t count = run_dense_count(c, mh, c->stream);
+    if (!xyz && !scan && !index && !hits) {  // the sizing call
+      *n = count;
+      return;
+    }
+    if (*n < count)
+      throw StatusError(FMX_E_SIZE, "dense map download: room for " + std::to_string(*n) + " of " +
+                                        std::to_string(count) + " voxels");
+    if (count) {
+      run_dense_compact(c, mh, count, c->stream);
+      std::vector<unsigned long long> tag;
+      if (scan || index) {
+        tag.resize(count);
+        FMX_HIP(hipMemcpyAsync(tag.data(), D.o_tag.p, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                               c->stream));
+      }
+      if (xyz)
+        FMX_HIP(hipMemcpyAsync(xyz, D.o_xyz.p, 3 * (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      if (hits) FMX_HIP(hipMemcpyAsync(hits, D.o_hits.p, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+      FMX_HIP(hipStreamSynchronize(c->stream));
+      for (size_t i = 0; i < tag.size(); ++i) {  // the host keeps the integration -> scan_idx table
+        if (scan) scan[i] = D.seq_scan.at((size_t)(tag[i] >> 32));
+        if (index) index[i] = (uint32_t)tag[i];
+      }
+    }
+    *n = count;
+  });
+}
+
+fmx_status fmx_dense_clear(fmx_ctx* c) {
+  return guard<false>(c, [&] {
+    auto& D = c->dense;
+    if (!D.on) throw StatusError(FMX_E_STATE, "the dense map is not enabled (fmx_dense_configure)");
+    dense_settle(c);
+    run_dense_clear(c, c->stream);
+    D.voxels = 0;
+    D.seq_scan.clear();
   });
 }
 

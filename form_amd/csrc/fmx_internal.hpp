@@ -223,6 +223,7 @@ enum ProfId {
   PROF_MOMENTS,
   PROF_DESKEW,
   PROF_ORGANIZE,
+  PROF_DENSE,
   PROF_COUNT
 };
 
@@ -560,6 +561,38 @@ struct fmx_ctx {
     fmx::DBuf<uint16_t> in_ring;
     fmx::DBuf<float> in_frac;
   } org;
+
+  // ---- dense voxel map of the registered scans (densemap.hip; fmx_dense_configure).  Off
+  // unless configured: no buffer below is then allocated and no entry point behaves differently.
+  struct Dense {
+    bool on = false;
+    bool used = false;             // an integration has run: the configuration is final
+    double voxel_w = 0.0, min2 = 0.0, max2 = 0.0;
+    uint32_t every = 1;
+    uint64_t max_voxels = 0, slots = 0;  // slots: the smallest power of two >= 2 * max_voxels
+    // the table, structure-of-arrays, exactly `slots` entries each (44 B per slot)
+    fmx::DBuf<unsigned long long> keys, tags;  // all-ones: empty / no representative yet
+    fmx::DBuf<uint32_t> hits;
+    fmx::DBuf<double> xyz;         // [slots][3]: the representative's world point
+    fmx::DBuf<uint32_t> slot_of;   // per point of the integration in flight: its slot, or the dropped marker
+    fmx::DBuf<uint32_t> cnt;       // {invalid, gated, out_of_range, voxels, fill ticket (2 words)}
+    fmx::HBuf<uint32_t> h_res;     // {added, merged, gated, out_of_range, invalid, voxels, -, completion word}
+    uint32_t flag_seq = 0;         // the completion word's last value
+    uint32_t pending = 0;          // ... of an integration queued and not yet waited for (else 0)
+    uint64_t voxels = 0;           // occupied slots (host copy, current between integrations)
+    std::vector<uint64_t> seq_scan;  // integration number (a tag's high word) -> the caller's scan_idx
+    fmx::DBuf<float4> in;          // device copy of a host scan (fmx_dense_integrate)
+    fmx::DBuf<float4> keep;        // register path: a host-announced scan, kept past the next one's DMA
+    // download: slots counted, then appended
+    fmx::DBuf<uint32_t> out_n;
+    fmx::HBuf<uint32_t> h_n;
+    fmx::DBuf<double> o_xyz;
+    fmx::DBuf<unsigned long long> o_tag;
+    fmx::DBuf<uint32_t> o_hits;
+    // what the last fmx_register_scan / fmx_register_cloud did (fmx_dense_last)
+    fmx_dense_counts last{};
+    int last_integrated = 0;
+  } dense;
 
   // ---- window keypoint store + maps
   fmx::Pool pool[2];
@@ -910,6 +943,16 @@ void run_deskew_cells(fmx_ctx* c, const float4* d_in, float4* d_out, const float
 // without d_frac), claim + gather on stream st; the counts reach c->org.h_cnt
 void run_organize(fmx_ctx* c, const float4* d_pts, const uint16_t* d_ring, const float* d_frac, size_t n,
                   float4* d_out, uint32_t* d_index, float* d_frac_out, hipStream_t st);
+// densemap.hip: claim + fill of n > 0 points at pose34 as integration number seq; the counts,
+// the voxel total and the completion word flag_seq reach c->dense.h_res (the caller has
+// checked the capacity rule)
+void run_dense_integrate(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, uint32_t seq,
+                         uint32_t flag_seq, hipStream_t st);
+// ... the number of voxels with hits >= min_hits (one launch, waits for it); those voxels
+// appended to c->dense.o_xyz / o_tag / o_hits (one launch, queued); the table emptied
+uint32_t run_dense_count(fmx_ctx* c, uint32_t min_hits, hipStream_t st);
+void run_dense_compact(fmx_ctx* c, uint32_t min_hits, uint32_t count, hipStream_t st);
+void run_dense_clear(fmx_ctx* c, hipStream_t st);
 // packed x, y, z (a staged host scan) -> float4 points with pad 0, on stream st
 void unpack_xyz(fmx_ctx* c, const float* d_packed, float4* d_out, size_t n, hipStream_t st);
 // st: stream to build on (default the context stream; register_scan uses the side

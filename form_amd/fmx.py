@@ -78,6 +78,20 @@ class _OrganizeCounts(C.Structure):
         return dict(placed=self.placed, displaced=self.displaced, off_grid=self.off_grid, invalid=self.invalid)
 
 
+class _DenseParams(C.Structure):
+    _fields_ = [("enable", C.c_int32), ("voxel_width", C.c_double), ("max_voxels", C.c_uint64),
+                ("min_norm_squared", C.c_double), ("max_norm_squared", C.c_double), ("every", C.c_uint32)]
+
+
+class _DenseCounts(C.Structure):
+    _fields_ = [("added", C.c_uint32), ("merged", C.c_uint32), ("gated", C.c_uint32), ("out_of_range", C.c_uint32),
+                ("invalid", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(added=self.added, merged=self.merged, gated=self.gated, out_of_range=self.out_of_range,
+                    invalid=self.invalid)
+
+
 class _Counts(C.Structure):
     _fields_ = [("planar", C.c_uint32), ("point", C.c_uint32), ("planar_selected", C.c_uint32)]
 
@@ -109,6 +123,8 @@ EXPORTED = [
     "fmx_deskew_configure", "fmx_deskew_set_twist", "fmx_deskew_last", "fmx_deskew",
     "fmx_organize_configure", "fmx_organize", "fmx_register_cloud", "fmx_deskew_cells",
     "fmx_corr_download", "fmx_pair_sort_plan",
+    "fmx_dense_configure", "fmx_dense_integrate", "fmx_dense_last", "fmx_dense_stats", "fmx_dense_download",
+    "fmx_dense_clear",
 ]
 
 PAIR_SORT_FORMS = ("none", "per-block", "tail-scanned", "scatter-scanned")
@@ -631,6 +647,70 @@ class Context:
         self.n_planar, self.n_point = c.planar, c.point
         return c.planar, c.point, cnt.as_dict()
 
+    # ---------------------------------------------------------------- dense voxel map
+    def dense_configure(self, enable: bool = True, voxel_width: float = 0.2, max_voxels: int = 1 << 22,
+                        min_norm_squared: float = 0.0, max_norm_squared: float = 0.0, every: int = 1):
+        """fmx_dense_configure (before the first registration or integration): a dense voxel
+        map of the registered scans, `max_voxels` voxels of width `voxel_width` at the most.
+        The gate defaults (both 0) to the extraction's range limits; `every`: the register
+        path integrates scans 0, every, 2 every, ..."""
+        p = _DenseParams()
+        p.enable = int(bool(enable))
+        p.voxel_width = float(voxel_width)
+        p.max_voxels = int(max_voxels)
+        p.min_norm_squared = float(min_norm_squared)
+        p.max_norm_squared = float(max_norm_squared)
+        p.every = int(every)
+        self._chk(self._L.fmx_dense_configure(self.h, C.byref(p)))
+        self._dense = True  # profile_read reports the "dense" id from here on
+
+    def dense_integrate(self, points, pose34, scan_idx: int = 0) -> dict:
+        """fmx_dense_integrate: (N, 4) float32 points (numpy, or a torch tensor on the host
+        or the device) into the map at pose34 (3 x 4).  Returns the counts (added, merged,
+        gated, out_of_range, invalid; they sum to N)."""
+        on_dev, ptr, n, keep = _scan_ptr(points)
+        pose = np.ascontiguousarray(pose34, np.float64).reshape(12)
+        if on_dev:
+            _ready(keep)
+        cnt = _DenseCounts()
+        self._chk(self._L.fmx_dense_integrate(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev), _p(pose),
+                                              C.c_uint64(scan_idx), C.byref(cnt)))
+        del keep
+        return cnt.as_dict()
+
+    def dense_last(self):
+        """fmx_dense_last: (counts dict, integrated) of the last register_scan /
+        register_cloud; integrated 1 done, 0 skipped by `every` (or the map is off), -1
+        refused for capacity."""
+        cnt = _DenseCounts()
+        flag = C.c_int(0)
+        self._chk(self._L.fmx_dense_last(self.h, C.byref(cnt), C.byref(flag)))
+        return cnt.as_dict(), int(flag.value)
+
+    def dense_stats(self) -> dict:
+        s = np.zeros(4, np.uint64)
+        self._chk(self._L.fmx_dense_stats(self.h, _p(s)))
+        return dict(voxels=int(s[0]), max_voxels=int(s[1]), integrations=int(s[2]), slots=int(s[3]))
+
+    def dense_download(self, min_hits: int = 1) -> dict:
+        """fmx_dense_download: the voxels with at least min_hits points, in no particular
+        order: points (N, 3) float64 in the world, scan (N,) uint64 and index (N,) uint32 of
+        each voxel's representative, hits (N,) uint32."""
+        n = C.c_uint32(0)
+        self._chk(self._L.fmx_dense_download(self.h, C.c_uint32(min_hits), None, None, None, None, C.byref(n)))
+        m = int(n.value)
+        pts = np.zeros((m, 3), np.float64)
+        scan = np.zeros(m, np.uint64)
+        index = np.zeros(m, np.uint32)
+        hits = np.zeros(m, np.uint32)
+        if m:
+            self._chk(self._L.fmx_dense_download(self.h, C.c_uint32(min_hits), _p(pts), _p(scan), _p(index), _p(hits),
+                                                 C.byref(n)))
+        return dict(points=pts[:n.value], scan=scan[:n.value], index=index[:n.value], hits=hits[:n.value])
+
+    def dense_clear(self):
+        self._chk(self._L.fmx_dense_clear(self.h))
+
     def current_pose(self) -> np.ndarray:
         T = np.zeros(12)
         self._chk(self._L.fmx_current_pose(self.h, _p(T)))
@@ -709,7 +789,12 @@ class Context:
         self._chk(self._L.fmx_profile_reset(self.h))
 
     def profile_read(self) -> dict:
+        """Per kernel id: ms, launches, bytes since the last reset.  The "dense" id is
+        listed once dense_configure has been called: a context that never configures the
+        map reads exactly as before."""
         n = self._L.fmx_profile_count()
+        if not getattr(self, "_dense", False) and self._L.fmx_profile_name(n - 1) == b"dense":
+            n -= 1
         ms = np.zeros(n)
         la = np.zeros(n, np.uint64)
         by = np.zeros(n)
@@ -902,6 +987,7 @@ class FORM:
         self._pose = np.eye(4)
         self._deskew = None  # set_deskew's arguments, applied by initialize()
         self._organize = None  # set_organize's arguments, applied by initialize()
+        self._dense = None  # set_dense_map's arguments, applied by initialize()
         self._scan_period = None  # seconds, from set_lidar_params when the parameters carry one
 
     @staticmethod
@@ -976,6 +1062,8 @@ class FORM:
             self._est.deskew_configure(*self._deskew)
         if self._organize is not None:
             self._est.organize_configure(**self._organize)
+        if self._dense is not None:
+            self._est.dense_configure(**self._dense)
         self._scan = -1
         self._pose = np.eye(4)
 
@@ -998,6 +1086,16 @@ class FORM:
                               elevation=None if elevation is None else np.array(elevation, np.float64).reshape(-1),
                               ring_to_row=None if ring_to_row is None else np.array(ring_to_row, np.int32).reshape(-1),
                               azimuth_offset=float(azimuth_offset), clockwise=bool(clockwise))
+
+    def set_dense_map(self, enable: bool = True, voxel_width: float = 0.2, max_voxels: int = 1 << 22, every: int = 1,
+                      min_norm_squared: float = 0.0, max_norm_squared: float = 0.0) -> None:
+        """A dense voxel map of the registered scans, kept on the device (fmx_dense_configure;
+        the reference's users build one on the host with scripts/rerun_map.py, so not a
+        pipeline YAML key).  Applied by initialize().  Every `every`-th scan is integrated at
+        its pose as add_lidar leaves it; the gate defaults to set_lidar_params' range limits."""
+        self._dense = dict(enable=bool(enable), voxel_width=float(voxel_width), max_voxels=int(max_voxels),
+                           every=int(every), min_norm_squared=float(min_norm_squared),
+                           max_norm_squared=float(max_norm_squared))
 
     def add_imu(self, mm) -> None:  # bindings.cpp:144 (unused)
         pass
@@ -1066,3 +1164,12 @@ class FORM:
             a[:, 3] = sc % 65536  # uint16 col, as add_lidar (map_download keeps the raw id)
             out[name] = a
         return out
+
+    def dense_map(self, min_hits: int = 1) -> dict:
+        """The dense voxel map (set_dense_map): one point per voxel with at least min_hits
+        points, as dense_download gives it: points (N, 3) in the world (lidar poses, as
+        map()), scan, index and hits; empty before initialize() or with the map off."""
+        if self._est is None or self._dense is None or not self._dense["enable"]:
+            return dict(points=np.zeros((0, 3)), scan=np.zeros(0, np.uint64), index=np.zeros(0, np.uint32),
+                        hits=np.zeros(0, np.uint32))
+        return self._est.dense_download(min_hits)

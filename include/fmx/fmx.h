@@ -419,6 +419,75 @@ fmx_status fmx_register_cloud(fmx_ctx* ctx, const fmx_cloud* cloud, fmx_feature_
 fmx_status fmx_deskew_cells(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
                             const float* fraction, const double twist[6], float* out_xyzw, int dst_on_device);
 
+/* ---------------- dense voxel map (no reference counterpart) -------------------
+ * The reference's users get a map of the registered points from scripts/rerun_map.py:
+ * every n-th scan of the trajectory, range-gated (dist2 > min2 and dist2 < max2), rotated
+ * into the world and concatenated on the host.  Opt-in, on the device: a fixed-capacity
+ * hash of world voxels that the registered scans are integrated into (DESIGN.md §Dense
+ * map).  Integrating n points p_i at pose T = [R | t] does, for each point:
+ *   invalid       x, y or z not finite, or x = y = z = 0;
+ *   gated         r2 = (x*x + y*y) + z*z (fp32, that order, no contraction), widened to
+ *                 double, unless r2 > min_norm_squared && r2 < max_norm_squared (both strict);
+ *   world point   w_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k in fp64;
+ *   voxel         c_k = floor(w_k / voxel_width) in fp64; out_of_range unless every
+ *                 |c_k| < 2^20 - 1.
+ * A voxel keeps `hits`, the number of valid in-range points that ever fell into it, and
+ * one representative: the point with the smallest (integration number, input index), its
+ * fp64 world point stored once and never changed.  The first integration to see a voxel
+ * owns it, within it the lowest index; later ones only add to hits.  The map's content
+ * does not depend on the order the device's threads run in.  The table has the smallest
+ * power of two >= 2 * max_voxels slots; an integration is refused (FMX_E_OOM, nothing
+ * launched, nothing changed) unless voxels + n <= max_voxels, so no point is ever dropped
+ * for lack of room.  The map is never pruned and never grows.  Never configured, or
+ * enable = 0: every other entry point behaves exactly as without this block. */
+typedef struct fmx_dense_params {
+  int32_t enable;            /* 0 = off */
+  double voxel_width;        /* > 0, finite */
+  uint64_t max_voxels;       /* > 0; FMX_E_INVAL past 2^29 */
+  double min_norm_squared;   /* both 0: the context's extraction values */
+  double max_norm_squared;
+  uint32_t every;            /* register path: integrate every n-th registered scan; 0 = 1 */
+} fmx_dense_params;
+typedef struct fmx_dense_counts {
+  uint32_t added;        /* new voxels */
+  uint32_t merged;       /* valid points that did not become a representative */
+  uint32_t gated;
+  uint32_t out_of_range;
+  uint32_t invalid;      /* the five sum to n */
+} fmx_dense_counts;
+/* Before the first registration and the first integration of the context (FMX_E_STATE
+ * afterwards).  Allocates the table (44 B per slot) and every per-scan buffer: FMX_E_OOM
+ * when that fails.  FMX_E_INVAL: a voxel width that is not finite and positive, max_voxels
+ * 0 or past 2^29, a gate that is NaN, negative or empty (min >= max). */
+fmx_status fmx_dense_configure(fmx_ctx* ctx, const fmx_dense_params* p);
+/* Stand-alone: integrate n_points < 2^32 points (host or device memory) at pose34 under the
+ * caller's scan_idx.  Returns once the counts are in (counts may be NULL).  FMX_E_STATE
+ * unless the map is configured and enabled; FMX_E_INVAL for a non-finite pose or NULL points
+ * with n_points > 0; FMX_E_OOM by the capacity rule above. */
+fmx_status fmx_dense_integrate(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                               const double pose34[12], uint64_t scan_idx, fmx_dense_counts* counts);
+/* Register path: with the map on, a successful fmx_register_scan or fmx_register_cloud of
+ * every `every`-th scan (scans 0, every, 2 every, ...) integrates the scan the extractor saw
+ * (the deskewed scan with deskewing on, the organized scan of a cloud: index is then the
+ * cell) at the pose fmx_current_pose returns after that call, under the scan's own index.
+ * The integration has read the scan when the registration returns.  A capacity refusal
+ * never fails the registration.  What the last registration did: its counts and
+ * *integrated = 1 integrated, 0 skipped by `every` (or the map is off), -1 refused for
+ * capacity.  Either pointer may be NULL. */
+fmx_status fmx_dense_last(fmx_ctx* ctx, fmx_dense_counts* counts, int* integrated);
+/* out = {voxels, max_voxels, integrations, slots}; all 0 when never configured. */
+fmx_status fmx_dense_stats(fmx_ctx* ctx, uint64_t out[4]);
+/* The voxels with hits >= min_hits (0 is taken as 1), in no particular order: xyz[3n] the
+ * representative's world point, scan[n] the scan_idx of the integration that owns the voxel,
+ * index[n] the representative's input index, hits[n].  Two calls, as for the keypoint map's
+ * download: with all four buffers NULL *n receives the count; with buffers (any may be
+ * NULL and is then skipped) *n is the capacity on entry (FMX_E_SIZE if too small, nothing
+ * written) and the count on return. */
+fmx_status fmx_dense_download(fmx_ctx* ctx, uint32_t min_hits, double* xyz, uint64_t* scan, uint32_t* index,
+                              uint32_t* hits, uint32_t* n);
+/* Empty the map; the integration counter restarts at 0. */
+fmx_status fmx_dense_clear(fmx_ctx* ctx);
+
 /* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
  * pose at the middle of the last registered sweep. */
 fmx_status fmx_current_pose(fmx_ctx* ctx, double pose34[12]);
