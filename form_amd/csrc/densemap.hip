@@ -22,7 +22,8 @@
 //           completion word to pinned host memory and re-arms the counters.
 //
 // The content of the map does not depend on the order the lanes run in: keys are only
-// ever inserted, the tag is a minimum, the hit count a sum, and a slot's point is written
+// ever inserted (between integrations a roll, further down, may rebuild the table from the
+// voxels it keeps), the tag is a minimum, the hit count a sum, and a slot's point is written
 // by exactly one lane.  The host keeps the load at or below 1/2 (it refuses an integration
 // unless voxels + n <= max_voxels, and slots >= 2 * max_voxels), so a probe sequence always
 // meets an empty slot.
@@ -234,6 +235,147 @@ __global__ __launch_bounds__(kDenseThreads) void k_dense_compact(const uint32_t*
   }
 }
 
+// ---- rolling (DESIGN.md §Dense map, Rolling; include/fmx/fmx.h, fmx_roll_evict).  The
+// voxels outside a box leave the table and the ones inside are put back by their keys: a
+// slot emptied in place would cut the probe chains that run through it (a later claim
+// would stop at the hole and insert the key behind it a second time), and a tombstone
+// would count towards the load that bounds the probe loops.  Three launches on one stream,
+// the kernel boundary the only ordering, as above.
+//
+//   count     every key: inside / outside, one atomic per wave and counter
+//   split     two walks per wave (as k_dense_compact): what it will move to each of the two
+//             streams, ONE returning atomic per stream for its place, then the copy.  The
+//             lane that moves a slot empties it (key, tag, hits); no other lane reads it in
+//             this launch, so the table is empty when the launch ends, without a memset.
+//   reinsert  one lane per kept voxel: the claim's probe with its own (distinct) key, then
+//             plain stores of tag, hits and point; sets the device's voxel total.
+//
+// A voxel is inside iff |v_k - cc_k| <= half_k on every axis, v decoded from the key, in
+// 64-bit integers (tests/roll_ref.py restates it).
+struct RollBox {
+  long long cc[3], half[3];
+};
+
+__device__ __forceinline__ bool roll_inside(unsigned long long key, const RollBox& b) {
+  const long long v[3] = {(long long)((key >> 42) & 0x1FFFFFull) - kDenseBias,
+                          (long long)((key >> 21) & 0x1FFFFFull) - kDenseBias, (long long)(key & 0x1FFFFFull) - kDenseBias};
+  bool in = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const long long d = v[k] - b.cc[k];
+    in = in && (d < 0 ? -d : d) <= b.half[k];
+  }
+  return in;
+}
+
+// out: {inside, outside}
+__global__ __launch_bounds__(kDenseThreads) void k_roll_count(const unsigned long long* __restrict__ keys, uint64_t slots,
+                                                              RollBox box, uint32_t* __restrict__ out) {
+  uint32_t n_in = 0, n_out = 0;
+  for (uint64_t base = (uint64_t)blockIdx.x * kDenseThreads; base < slots; base += (uint64_t)gridDim.x * kDenseThreads) {
+    const uint64_t s = base + threadIdx.x;
+    const unsigned long long k = s < slots ? keys[s] : kDenseEmpty;
+    const bool occ = k != kDenseEmpty, in = occ && roll_inside(k, box);
+    n_in += (uint32_t)__popcll(__ballot(in));  // the same in every lane of the wave
+    n_out += (uint32_t)__popcll(__ballot(occ && !in));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (n_in) atomicAdd(&out[0], n_in);
+    if (n_out) atomicAdd(&out[1], n_out);
+  }
+}
+
+// cur: {evicted, kept} cursors; cap_e / cap_k: the room in the outputs (e_*) and the staging list (s_*)
+__global__ __launch_bounds__(kDenseThreads) void k_roll_split(
+    unsigned long long* keys, unsigned long long* tags, uint32_t* hits, const double* __restrict__ xyz, uint64_t slots,
+    RollBox box, uint32_t cap_e, uint32_t cap_k, uint32_t* __restrict__ cur,
+    double* __restrict__ e_xyz, unsigned long long* __restrict__ e_tag, uint32_t* __restrict__ e_hits,
+    unsigned long long* __restrict__ s_key, unsigned long long* __restrict__ s_tag, uint32_t* __restrict__ s_hits,
+    double* __restrict__ s_xyz) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t first = (uint64_t)blockIdx.x * kDenseThreads, step = (uint64_t)gridDim.x * kDenseThreads;
+  uint32_t n_e = 0, n_k = 0;
+  for (uint64_t base = first; base < slots; base += step) {
+    const uint64_t s = base + threadIdx.x;
+    const unsigned long long k = s < slots ? keys[s] : kDenseEmpty;
+    const bool occ = k != kDenseEmpty, in = occ && roll_inside(k, box);
+    n_k += (uint32_t)__popcll(__ballot(in));
+    n_e += (uint32_t)__popcll(__ballot(occ && !in));
+  }
+  if (!n_e && !n_k) return;  // (the whole wave)
+  uint32_t at_e = 0, at_k = 0;
+  if (lane == 0) {
+    if (n_e) at_e = atomicAdd(&cur[0], n_e);
+    if (n_k) at_k = atomicAdd(&cur[1], n_k);
+  }
+  at_e = (uint32_t)__shfl((int)at_e, 0, 64);
+  at_k = (uint32_t)__shfl((int)at_k, 0, 64);
+  for (uint64_t base = first; base < slots; base += step) {
+    const uint64_t s = base + threadIdx.x;
+    const unsigned long long k = s < slots ? keys[s] : kDenseEmpty;  // this lane's own slot: not yet emptied
+    const bool occ = k != kDenseEmpty, in = occ && roll_inside(k, box);
+    const unsigned long long b_k = __ballot(in), b_e = __ballot(occ && !in);
+    if (occ) {
+      const unsigned long long t = tags[s];
+      const uint32_t h = hits[s];
+      const double x = xyz[3 * s + 0], y = xyz[3 * s + 1], z = xyz[3 * s + 2];
+      if (in) {
+        const uint32_t o = at_k + (uint32_t)__popcll(b_k & lanemask_lt());
+        if (o < cap_k) {  // (the count pass sized both: never false)
+          s_key[o] = k;
+          s_tag[o] = t;
+          s_hits[o] = h;
+          s_xyz[3 * (size_t)o + 0] = x;
+          s_xyz[3 * (size_t)o + 1] = y;
+          s_xyz[3 * (size_t)o + 2] = z;
+        }
+      } else {
+        const uint32_t o = at_e + (uint32_t)__popcll(b_e & lanemask_lt());
+        if (o < cap_e) {
+          e_tag[o] = t;
+          e_hits[o] = h;
+          e_xyz[3 * (size_t)o + 0] = x;
+          e_xyz[3 * (size_t)o + 1] = y;
+          e_xyz[3 * (size_t)o + 2] = z;
+        }
+      }
+      keys[s] = kDenseEmpty;
+      tags[s] = ~0ull;
+      hits[s] = 0u;
+    }
+    at_k += (uint32_t)__popcll(b_k);
+    at_e += (uint32_t)__popcll(b_e);
+  }
+}
+
+// The kept voxels back into the (empty) table; cnt[3]: the device's voxel total (k_dense_fill adds to it).
+__global__ __launch_bounds__(kDenseThreads) void k_roll_reinsert(
+    const unsigned long long* __restrict__ s_key, const unsigned long long* __restrict__ s_tag,
+    const uint32_t* __restrict__ s_hits, const double* __restrict__ s_xyz, uint32_t kept, unsigned long long* keys,
+    unsigned long long* __restrict__ tags, uint32_t* __restrict__ hits, double* __restrict__ xyz, uint32_t slot_mask,
+    uint32_t* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * (uint32_t)kDenseThreads + threadIdx.x;
+  if (i == 0) cnt[3] = kept;
+  if (i >= kept) return;
+  const unsigned long long key = s_key[i];
+  uint32_t h = (uint32_t)mix64(key) & slot_mask;
+  // (bounded by the table: kept <= max_voxels leaves half the slots empty; the keys are
+  // distinct, so a CAS wins an empty slot or meets another key)
+  for (uint32_t probe = 0; probe <= slot_mask; ++probe) {
+    unsigned long long k = keys[h];
+    if (k == kDenseEmpty) k = atomicCAS(&keys[h], kDenseEmpty, key);
+    if (k == kDenseEmpty) {
+      tags[h] = s_tag[i];
+      hits[h] = s_hits[i];
+      xyz[3 * (size_t)h + 0] = s_xyz[3 * (size_t)i + 0];
+      xyz[3 * (size_t)h + 1] = s_xyz[3 * (size_t)i + 1];
+      xyz[3 * (size_t)h + 2] = s_xyz[3 * (size_t)i + 2];
+      return;
+    }
+    h = (h + 1) & slot_mask;
+  }
+}
+
 static DenseArgs dense_args(const fmx_ctx* c, const double* pose34) {
   const auto& D = c->dense;
   DenseArgs a{};
@@ -312,6 +454,63 @@ void run_dense_clear(fmx_ctx* c, hipStream_t st) {
   FMX_HIP(hipMemsetAsync(D.tags.p, 0xFF, D.slots * sizeof(unsigned long long), st));
   FMX_HIP(hipMemsetAsync(D.hits.p, 0, D.slots * sizeof(uint32_t), st));
   FMX_HIP(hipMemsetAsync(D.cnt.p, 0, 8 * sizeof(uint32_t), st));
+}
+
+static RollBox roll_box(const long long cc[3], const uint32_t half[3]) {
+  RollBox b{};
+  for (int k = 0; k < 3; ++k) {
+    b.cc[k] = cc[k];
+    b.half[k] = (long long)half[k];
+  }
+  return b;
+}
+
+// {inside, outside} of the box into out (one launch; waits).
+void run_roll_count(fmx_ctx* c, const long long cc[3], const uint32_t half[3], uint32_t out[2], hipStream_t st) {
+  auto& D = c->dense;
+  D.roll.n.ensure(4);
+  D.h_n.ensure(2);
+  FMX_HIP(hipMemsetAsync(D.roll.n.p, 0, 4 * sizeof(uint32_t), st));
+  {
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (D.slots + kDenseThreads - 1) / kDenseThreads);
+    ProfScope ps(c->prof, PROF_DENSE, (double)D.slots * 8.0, st);  // every slot's key
+    hipLaunchKernelGGL(k_roll_count, dim3(blocks), dim3(kDenseThreads), 0, st, D.keys.p, D.slots, roll_box(cc, half),
+                       D.roll.n.p);
+    FMX_HIP(hipGetLastError());
+  }
+  FMX_HIP(hipMemcpyAsync(D.h_n.p, D.roll.n.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  FMX_HIP(hipStreamSynchronize(st));
+  out[0] = D.h_n.p[0];
+  out[1] = D.h_n.p[1];
+}
+
+// After run_roll_count of the same box (its cursors are still zero; the outputs and the
+// staging list hold evicted / kept entries): the evicted voxels appended to c->dense.o_xyz /
+// o_tag / o_hits, the kept ones put back, the device's voxel total set (queued only).
+void run_roll_rebuild(fmx_ctx* c, const long long cc[3], const uint32_t half[3], uint32_t kept, uint32_t evicted,
+                      hipStream_t st) {
+  auto& D = c->dense;
+  auto& Rl = D.roll;
+  {
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (D.slots + kDenseThreads - 1) / kDenseThreads);
+    // every slot's key, twice (2 * 8) + per evicted voxel its tag, hits and point read and
+    // written, its slot emptied (2 * 36 + 20) + per kept voxel the same and its key written (+ 8)
+    ProfScope ps(c->prof, PROF_DENSE, (double)D.slots * 16.0 + (double)evicted * 92.0 + (double)kept * 100.0, st);
+    hipLaunchKernelGGL(k_roll_split, dim3(blocks), dim3(kDenseThreads), 0, st, D.keys.p, D.tags.p, D.hits.p, D.xyz.p,
+                       D.slots, roll_box(cc, half), evicted, kept, Rl.n.p + 2, D.o_xyz.p, D.o_tag.p, D.o_hits.p, Rl.s_key.p,
+                       Rl.s_tag.p, Rl.s_hits.p, Rl.s_xyz.p);
+    FMX_HIP(hipGetLastError());
+  }
+  if (kept) {
+    const uint32_t blocks = (kept + kDenseThreads - 1) / kDenseThreads;
+    // the staged voxel read (44) and written: key, tag, hits, point (44); probes past the home slot not counted
+    ProfScope ps(c->prof, PROF_DENSE, (double)kept * 88.0, st);
+    hipLaunchKernelGGL(k_roll_reinsert, dim3(blocks), dim3(kDenseThreads), 0, st, Rl.s_key.p, Rl.s_tag.p, Rl.s_hits.p,
+                       Rl.s_xyz.p, kept, D.keys.p, D.tags.p, D.hits.p, D.xyz.p, (uint32_t)(D.slots - 1), D.cnt.p);
+    FMX_HIP(hipGetLastError());
+  } else {
+    FMX_HIP(hipMemsetAsync(D.cnt.p + 3, 0, sizeof(uint32_t), st));
+  }
 }
 
 }  // namespace fmx

@@ -1379,6 +1379,7 @@ void dense_release(fmx_ctx* c) {
   D.xyz.release();
   D.max_voxels = D.slots = D.voxels = 0;
   D.seq_scan.clear();
+  D.roll.on = D.roll.have_centre = false;  // (a roll configuration belongs to the map it was made for)
 }
 // Queue the integration of the n device points at d (the capacity rule checked by the
 // caller) on the context stream; returns the completion word's value to wait for, 0 when
@@ -1418,6 +1419,111 @@ void dense_settle(fmx_ctx* c) {
   if (c->dense.pending) dense_finish(c, c->dense.pending, nullptr);
 }
 
+// ---- rolling (fmx_roll_*; densemap.hip)
+// The centre voxel, the integration's own expression; false when it is out of the key range.
+bool roll_centre_voxel(const fmx_ctx* c, const double centre[3], long long cc[3]) {
+  for (int k = 0; k < 3; ++k) {
+    const double v = std::floor(centre[k] / c->dense.voxel_w);
+    if (!(std::fabs(v) < 1048575.0)) return false;  // 2^20 - 1, in fp64 before the cast
+    cc[k] = (long long)v;
+  }
+  return true;
+}
+// DBuf::ensure with a failed allocation reported as a capacity error, not a HIP one.
+template <class T>
+void roll_ensure(DBuf<T>& b, size_t n) {
+  try {
+    b.ensure(n);
+  } catch (const HipError&) {
+    (void)hipGetLastError();
+    throw StatusError(FMX_E_OOM, "dense map roll: device allocation of " + std::to_string(n * sizeof(T)) + " bytes failed");
+  }
+}
+// After run_roll_count gave {kept, evicted} with evicted > 0: size the buffers (FMX_E_OOM
+// with nothing changed), split, reinsert, take the new voxel total.  Queued only.
+void roll_rebuild(fmx_ctx* c, const long long cc[3], const uint32_t half[3], uint32_t kept, uint32_t evicted) {
+  auto& D = c->dense;
+  roll_ensure(D.o_xyz, 3 * (size_t)evicted);
+  roll_ensure(D.o_tag, evicted);
+  roll_ensure(D.o_hits, evicted);
+  if (kept) {
+    roll_ensure(D.roll.s_key, kept);
+    roll_ensure(D.roll.s_tag, kept);
+    roll_ensure(D.roll.s_hits, kept);
+    roll_ensure(D.roll.s_xyz, 3 * (size_t)kept);
+  }
+  run_roll_rebuild(c, cc, half, kept, evicted, c->stream);
+  D.voxels = kept;
+}
+// The evicted voxels of the last roll_rebuild to the host (any pointer may be null); waits.
+void roll_fetch(fmx_ctx* c, uint32_t count, double* xyz, uint64_t* scan, uint32_t* index, uint32_t* hits) {
+  auto& D = c->dense;
+  std::vector<unsigned long long> tag;
+  if (scan || index) {
+    tag.resize(count);
+    FMX_HIP(hipMemcpyAsync(tag.data(), D.o_tag.p, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                           c->stream));
+  }
+  if (xyz) FMX_HIP(hipMemcpyAsync(xyz, D.o_xyz.p, 3 * (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (hits) FMX_HIP(hipMemcpyAsync(hits, D.o_hits.p, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  FMX_HIP(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < tag.size(); ++i) {
+    if (scan) scan[i] = D.seq_scan.at((size_t)(tag[i] >> 32));
+    if (index) index[i] = (uint32_t)tag[i];
+  }
+}
+// Register path, at the start of scan j >= 1's registration (the previous integration is
+// settled): p is scan j - 1's final translation; due: scan j would be integrated by `every`.
+// Never fails the registration for a centre out of range or a failed allocation.
+void roll_on_register(fmx_ctx* c, uint64_t j, const double p[3], bool due, size_t n) {
+  auto& D = c->dense;
+  auto& Rl = D.roll;
+  if (!Rl.have_centre) {
+    std::memcpy(Rl.centre, p, sizeof(Rl.centre));
+    Rl.have_centre = true;
+    return;
+  }
+  double far = 0.0;
+  for (int k = 0; k < 3; ++k) far = std::max(far, std::fabs(p[k] - Rl.centre[k]));
+  if (!(far >= Rl.step) && !(due && D.voxels + n > D.max_voxels)) return;
+  long long cc[3];
+  if (!roll_centre_voxel(c, p, cc)) return;
+  uint32_t io[2];
+  run_roll_count(c, cc, Rl.half, io, c->stream);
+  const uint32_t kept = io[0], evicted = io[1];
+  if (evicted) {
+    const size_t at = Rl.sp_scan.size();
+    try {
+      if (Rl.spill) {
+        Rl.sp_xyz.reserve(3 * (at + evicted));
+        Rl.sp_scan.reserve(at + evicted);
+        Rl.sp_index.reserve(at + evicted);
+        Rl.sp_hits.reserve(at + evicted);
+      }
+      roll_rebuild(c, cc, Rl.half, kept, evicted);
+    } catch (const std::bad_alloc&) {
+      return;
+    } catch (const StatusError& e) {
+      if (e.st == FMX_E_OOM) return;
+      throw;
+    }
+    if (Rl.spill) {
+      Rl.sp_xyz.resize(3 * (at + evicted));  // within the reserved room: no allocation
+      Rl.sp_scan.resize(at + evicted);
+      Rl.sp_index.resize(at + evicted);
+      Rl.sp_hits.resize(at + evicted);
+      roll_fetch(c, evicted, Rl.sp_xyz.data() + 3 * at, Rl.sp_scan.data() + at, Rl.sp_index.data() + at,
+                 Rl.sp_hits.data() + at);
+    }
+  }
+  std::memcpy(Rl.centre, p, sizeof(Rl.centre));
+  Rl.rolls++;
+  Rl.evicted_total += evicted;
+  Rl.last_kept = kept;
+  Rl.last_evicted = evicted;
+  Rl.last_scan = j;
+}
+
 // dsk_cells (fmx_register_cloud with deskewing on): the scan's per-cell sweep fractions
 void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feature_counts* out,
                    const float* dsk_cells = nullptr) {
@@ -1451,6 +1557,13 @@ void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feat
   dense_settle(c);
   DM.last = fmx_dense_counts{};
   DM.last_integrated = 0;
+  // Rolling (opt-in): the voxels outside the box about the previous scan's pose leave the
+  // map before the capacity rule looks at it
+  if (DM.on && DM.roll.on && e.init) {
+    const double* m = e.values.at(e.scan).m;
+    const double p[3] = {m[3], m[7], m[11]};
+    roll_on_register(c, j, p, j % DM.every == 0, n);
+  }
   const bool dense_go = DM.on && j % DM.every == 0 && DM.voxels + n <= DM.max_voxels;
   if (DM.on && j % DM.every == 0 && !dense_go) DM.last_integrated = -1;
   bool took_pf = false;
@@ -2677,6 +2790,115 @@ fmx_status fmx_dense_clear(fmx_ctx* c) {
     run_dense_clear(c, c->stream);
     D.voxels = 0;
     D.seq_scan.clear();
+    D.roll.have_centre = false;  // (the spill holds scan_idx values: it stays)
+  });
+}
+
+// ---- rolling the dense map (densemap.hip)
+namespace {
+void roll_need_map(const fmx_ctx* c) {
+  if (!c->dense.on) throw StatusError(FMX_E_STATE, "the dense map is not enabled (fmx_dense_configure)");
+}
+void roll_check_box(const fmx_ctx* c, const double* centre, const uint32_t* half, long long cc[3]) {
+  if (!centre || !half) throw StatusError(FMX_E_INVAL, "null roll centre or half-extents");
+  for (int k = 0; k < 3; ++k) {
+    if (!std::isfinite(centre[k])) throw StatusError(FMX_E_INVAL, "non-finite roll centre");
+    if (half[k] > (1u << 21)) throw StatusError(FMX_E_INVAL, "roll half-extents are at most 2^21 voxels");
+  }
+  if (!roll_centre_voxel(c, centre, cc)) throw StatusError(FMX_E_INVAL, "the roll centre's voxel is out of range");
+}
+}  // namespace
+
+fmx_status fmx_roll_configure(fmx_ctx* c, const fmx_roll_params* p) {
+  return guard<false>(c, [&] {
+    if (!p) throw StatusError(FMX_E_INVAL, "null roll parameters");
+    roll_need_map(c);
+    for (int k = 0; k < 3; ++k)
+      if (p->half[k] > (1u << 21)) throw StatusError(FMX_E_INVAL, "roll half-extents are at most 2^21 voxels");
+    if (!(p->step >= 0.0) || !std::isfinite(p->step)) throw StatusError(FMX_E_INVAL, "the roll step must be finite and >= 0");
+    auto& Rl = c->dense.roll;
+    Rl.on = p->enable != 0;
+    for (int k = 0; k < 3; ++k) Rl.half[k] = p->half[k];
+    Rl.step = p->step;
+    Rl.spill = p->spill != 0;
+    Rl.have_centre = false;
+  });
+}
+
+fmx_status fmx_roll_count(fmx_ctx* c, const double centre[3], const uint32_t half[3], uint64_t out[2]) {
+  return guard<false>(c, [&] {
+    roll_need_map(c);
+    if (!out) throw StatusError(FMX_E_INVAL, "null output");
+    long long cc[3];
+    roll_check_box(c, centre, half, cc);
+    dense_settle(c);
+    uint32_t io[2];
+    run_roll_count(c, cc, half, io, c->stream);
+    out[0] = io[0];
+    out[1] = io[1];
+  });
+}
+
+fmx_status fmx_roll_evict(fmx_ctx* c, const double centre[3], const uint32_t half[3], double* xyz, uint64_t* scan,
+                          uint32_t* index, uint32_t* hits, uint32_t* n) {
+  return guard<false>(c, [&] {
+    roll_need_map(c);
+    const bool any = xyz || scan || index || hits;
+    if (any && !n) throw StatusError(FMX_E_INVAL, "null count");
+    long long cc[3];
+    roll_check_box(c, centre, half, cc);
+    dense_settle(c);
+    uint32_t io[2];
+    run_roll_count(c, cc, half, io, c->stream);
+    const uint32_t kept = io[0], evicted = io[1];
+    if (any && *n < evicted)
+      throw StatusError(FMX_E_SIZE, "dense map roll: room for " + std::to_string(*n) + " of " + std::to_string(evicted) +
+                                        " evicted voxels");
+    if (evicted) {
+      roll_rebuild(c, cc, half, kept, evicted);
+      if (any) roll_fetch(c, evicted, xyz, scan, index, hits);
+    }
+    if (n) *n = evicted;
+  });
+}
+
+fmx_status fmx_roll_drain(fmx_ctx* c, double* xyz, uint64_t* scan, uint32_t* index, uint32_t* hits, uint32_t* n) {
+  return guard<false>(c, [&] {
+    roll_need_map(c);
+    if (!n) throw StatusError(FMX_E_INVAL, "null count");
+    auto& Rl = c->dense.roll;
+    if (Rl.sp_scan.size() > 0xFFFFFFFFull) throw StatusError(FMX_E_SIZE, "the spill holds more than 2^32 - 1 voxels");
+    const uint32_t count = (uint32_t)Rl.sp_scan.size();
+    if (!xyz && !scan && !index && !hits) {  // the sizing call
+      *n = count;
+      return;
+    }
+    if (*n < count)
+      throw StatusError(FMX_E_SIZE, "roll drain: room for " + std::to_string(*n) + " of " + std::to_string(count) + " voxels");
+    if (count) {
+      if (xyz) std::memcpy(xyz, Rl.sp_xyz.data(), 3 * (size_t)count * sizeof(double));
+      if (scan) std::memcpy(scan, Rl.sp_scan.data(), (size_t)count * sizeof(uint64_t));
+      if (index) std::memcpy(index, Rl.sp_index.data(), (size_t)count * sizeof(uint32_t));
+      if (hits) std::memcpy(hits, Rl.sp_hits.data(), (size_t)count * sizeof(uint32_t));
+    }
+    Rl.sp_xyz.clear();
+    Rl.sp_scan.clear();
+    Rl.sp_index.clear();
+    Rl.sp_hits.clear();
+    *n = count;
+  });
+}
+
+fmx_status fmx_roll_stats(fmx_ctx* c, uint64_t out[6]) {
+  return guard<false>(c, [&] {
+    if (!out) throw StatusError(FMX_E_INVAL, "null output");
+    const auto& Rl = c->dense.roll;
+    out[0] = Rl.rolls;
+    out[1] = Rl.evicted_total;
+    out[2] = Rl.sp_scan.size();
+    out[3] = Rl.last_kept;
+    out[4] = Rl.last_evicted;
+    out[5] = Rl.last_scan;
   });
 }
 

@@ -592,6 +592,25 @@ struct fmx_ctx {
     // what the last fmx_register_scan / fmx_register_cloud did (fmx_dense_last)
     fmx_dense_counts last{};
     int last_integrated = 0;
+    // rolling (fmx_roll_*): nothing below is allocated, and nothing launched, unless one of
+    // those entry points is called
+    struct Roll {
+      bool on = false, spill = false;  // fmx_roll_configure
+      uint32_t half[3] = {0, 0, 0};
+      double step = 0.0;
+      bool have_centre = false;        // register path: the translation the last roll (or the first look) saw
+      double centre[3] = {0.0, 0.0, 0.0};
+      uint64_t rolls = 0, evicted_total = 0, last_kept = 0, last_evicted = 0, last_scan = 0;
+      // the host spill: resolved scan_idx values, not tags (a later clear cannot invalidate it)
+      std::vector<double> sp_xyz;
+      std::vector<uint64_t> sp_scan;
+      std::vector<uint32_t> sp_index, sp_hits;
+      fmx::DBuf<uint32_t> n;           // {inside, outside, evicted cursor, kept cursor}
+      // the kept voxels between the split and the reinsert
+      fmx::DBuf<unsigned long long> s_key, s_tag;
+      fmx::DBuf<uint32_t> s_hits;
+      fmx::DBuf<double> s_xyz;
+    } roll;
   } dense;
 
   // ---- window keypoint store + maps
@@ -953,6 +972,13 @@ void run_dense_integrate(fmx_ctx* c, const float4* d_pts, size_t n, const double
 uint32_t run_dense_count(fmx_ctx* c, uint32_t min_hits, hipStream_t st);
 void run_dense_compact(fmx_ctx* c, uint32_t min_hits, uint32_t count, hipStream_t st);
 void run_dense_clear(fmx_ctx* c, hipStream_t st);
+// ... rolling: {inside, outside} of the box of voxels |v - cc| <= half (one launch, waits for
+// it); then, with c->dense.o_* sized to `evicted` and c->dense.roll.s_* to `kept`, the evicted
+// voxels appended to o_*, the kept ones put back into the emptied table and the device's
+// voxel total set (two launches, one when kept is 0; queued)
+void run_roll_count(fmx_ctx* c, const long long cc[3], const uint32_t half[3], uint32_t out[2], hipStream_t st);
+void run_roll_rebuild(fmx_ctx* c, const long long cc[3], const uint32_t half[3], uint32_t kept, uint32_t evicted,
+                      hipStream_t st);
 // packed x, y, z (a staged host scan) -> float4 points with pad 0, on stream st
 void unpack_xyz(fmx_ctx* c, const float* d_packed, float4* d_out, size_t n, hipStream_t st);
 // st: stream to build on (default the context stream; register_scan uses the side

@@ -14,6 +14,7 @@ import or the constructor raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass, fields
 
@@ -92,6 +93,10 @@ class _DenseCounts(C.Structure):
                     invalid=self.invalid)
 
 
+class _RollParams(C.Structure):
+    _fields_ = [("enable", C.c_int32), ("half", C.c_uint32 * 3), ("step", C.c_double), ("spill", C.c_int32)]
+
+
 class _Counts(C.Structure):
     _fields_ = [("planar", C.c_uint32), ("point", C.c_uint32), ("planar_selected", C.c_uint32)]
 
@@ -125,6 +130,7 @@ EXPORTED = [
     "fmx_corr_download", "fmx_pair_sort_plan",
     "fmx_dense_configure", "fmx_dense_integrate", "fmx_dense_last", "fmx_dense_stats", "fmx_dense_download",
     "fmx_dense_clear",
+    "fmx_roll_configure", "fmx_roll_count", "fmx_roll_evict", "fmx_roll_drain", "fmx_roll_stats",
 ]
 
 PAIR_SORT_FORMS = ("none", "per-block", "tail-scanned", "scatter-scanned")
@@ -711,6 +717,66 @@ class Context:
     def dense_clear(self):
         self._chk(self._L.fmx_dense_clear(self.h))
 
+    # ---------------------------------------------------------------- rolling the dense map
+    @staticmethod
+    def _roll_box(centre, half):
+        return (np.ascontiguousarray(centre, np.float64).reshape(3),
+                np.ascontiguousarray([int(h) for h in half], np.uint32).reshape(3))
+
+    def roll_configure(self, enable: bool = True, half=(0, 0, 0), step: float = 0.0, spill: bool = True):
+        """fmx_roll_configure: the register path rolls the dense map about the previous
+        scan's pose once it has moved `step` metres on an axis (or when the next integration
+        would not fit), keeping the voxels within `half` (three voxel counts) of it."""
+        p = _RollParams()
+        p.enable = int(bool(enable))
+        for k in range(3):
+            p.half[k] = int(half[k])
+        p.step = float(step)
+        p.spill = int(bool(spill))
+        self._chk(self._L.fmx_roll_configure(self.h, C.byref(p)))
+
+    def roll_count(self, centre, half):
+        """fmx_roll_count: (inside, outside) of the box; changes nothing."""
+        c, h = self._roll_box(centre, half)
+        out = np.zeros(2, np.uint64)
+        self._chk(self._L.fmx_roll_count(self.h, _p(c), _p(h), _p(out)))
+        return int(out[0]), int(out[1])
+
+    def roll_evict(self, centre, half, discard: bool = False) -> dict:
+        """fmx_roll_evict: the voxels outside the box leave the map and are returned like
+        dense_download's (empty arrays with discard=True)."""
+        c, h = self._roll_box(centre, half)
+        m = 0 if discard else self.roll_count(c, h)[1]
+        pts = np.zeros((m, 3), np.float64)
+        scan = np.zeros(m, np.uint64)
+        index = np.zeros(m, np.uint32)
+        hits = np.zeros(m, np.uint32)
+        n = C.c_uint32(m)
+        if discard:
+            self._chk(self._L.fmx_roll_evict(self.h, _p(c), _p(h), None, None, None, None, C.byref(n)))
+        elif m:
+            self._chk(self._L.fmx_roll_evict(self.h, _p(c), _p(h), _p(pts), _p(scan), _p(index), _p(hits), C.byref(n)))
+        return dict(points=pts[:m], scan=scan[:m], index=index[:m], hits=hits[:m])
+
+    def roll_drain(self) -> dict:
+        """fmx_roll_drain: the voxels the register path's rolls evicted since the last drain."""
+        n = C.c_uint32(0)
+        self._chk(self._L.fmx_roll_drain(self.h, None, None, None, None, C.byref(n)))
+        m = int(n.value)
+        pts = np.zeros((m, 3), np.float64)
+        scan = np.zeros(m, np.uint64)
+        index = np.zeros(m, np.uint32)
+        hits = np.zeros(m, np.uint32)
+        if m:
+            self._chk(self._L.fmx_roll_drain(self.h, _p(pts), _p(scan), _p(index), _p(hits), C.byref(n)))
+        return dict(points=pts[:n.value], scan=scan[:n.value], index=index[:n.value], hits=hits[:n.value])
+
+    def roll_stats(self) -> dict:
+        s = np.zeros(6, np.uint64)
+        self._chk(self._L.fmx_roll_stats(self.h, _p(s)))
+        return dict(rolls=int(s[0]), evicted=int(s[1]), spilled=int(s[2]), last_kept=int(s[3]), last_evicted=int(s[4]),
+                    last_scan=int(s[5]))
+
     def current_pose(self) -> np.ndarray:
         T = np.zeros(12)
         self._chk(self._L.fmx_current_pose(self.h, _p(T)))
@@ -988,6 +1054,7 @@ class FORM:
         self._deskew = None  # set_deskew's arguments, applied by initialize()
         self._organize = None  # set_organize's arguments, applied by initialize()
         self._dense = None  # set_dense_map's arguments, applied by initialize()
+        self._roll = None  # set_dense_roll's arguments, applied by initialize() after the dense map
         self._scan_period = None  # seconds, from set_lidar_params when the parameters carry one
 
     @staticmethod
@@ -1064,6 +1131,12 @@ class FORM:
             self._est.organize_configure(**self._organize)
         if self._dense is not None:
             self._est.dense_configure(**self._dense)
+        if self._roll is not None:
+            if self._dense is None:
+                raise ValueError("set_dense_roll needs set_dense_map")
+            w = self._dense["voxel_width"]
+            half = [int(math.ceil(h / w)) for h in self._roll["half_extent_m"]]
+            self._est.roll_configure(self._roll["enable"], half, self._roll["step_m"], self._roll["spill"])
         self._scan = -1
         self._pose = np.eye(4)
 
@@ -1096,6 +1169,15 @@ class FORM:
         self._dense = dict(enable=bool(enable), voxel_width=float(voxel_width), max_voxels=int(max_voxels),
                            every=int(every), min_norm_squared=float(min_norm_squared),
                            max_norm_squared=float(max_norm_squared))
+
+    def set_dense_roll(self, enable: bool = True, half_extent_m=50.0, step_m: float = 2.0, spill: bool = True) -> None:
+        """Roll the dense map with the sensor (fmx_roll_configure): once the pose has moved
+        step_m on an axis, the voxels farther than half_extent_m (one number, or one per axis;
+        ceil(half_extent_m / voxel_width) voxels) from it leave the device.  With spill they
+        wait for dense_evicted(), else they are dropped.  Applied by initialize()."""
+        h = np.broadcast_to(np.asarray(half_extent_m, np.float64), (3,))
+        self._roll = dict(enable=bool(enable), half_extent_m=[float(v) for v in h], step_m=float(step_m),
+                          spill=bool(spill))
 
     def add_imu(self, mm) -> None:  # bindings.cpp:144 (unused)
         pass
@@ -1173,3 +1255,11 @@ class FORM:
             return dict(points=np.zeros((0, 3)), scan=np.zeros(0, np.uint64), index=np.zeros(0, np.uint32),
                         hits=np.zeros(0, np.uint32))
         return self._est.dense_download(min_hits)
+
+    def dense_evicted(self) -> dict:
+        """The voxels the rolling map (set_dense_roll) has evicted since the last call, as
+        dense_map gives them; empty before initialize() or with rolling off."""
+        if self._est is None or self._dense is None or not self._dense["enable"] or self._roll is None:
+            return dict(points=np.zeros((0, 3)), scan=np.zeros(0, np.uint64), index=np.zeros(0, np.uint32),
+                        hits=np.zeros(0, np.uint32))
+        return self._est.roll_drain()

@@ -438,7 +438,8 @@ fmx_status fmx_deskew_cells(fmx_ctx* ctx, const float* xyzw, size_t n_points, in
  * does not depend on the order the device's threads run in.  The table has the smallest
  * power of two >= 2 * max_voxels slots; an integration is refused (FMX_E_OOM, nothing
  * launched, nothing changed) unless voxels + n <= max_voxels, so no point is ever dropped
- * for lack of room.  The map is never pruned and never grows.  Never configured, or
+ * for lack of room.  The table never grows; the map is pruned only by the rolling block
+ * below, and only for a caller who asks for it.  Never configured, or
  * enable = 0: every other entry point behaves exactly as without this block. */
 typedef struct fmx_dense_params {
   int32_t enable;            /* 0 = off */
@@ -485,8 +486,59 @@ fmx_status fmx_dense_stats(fmx_ctx* ctx, uint64_t out[4]);
  * written) and the count on return. */
 fmx_status fmx_dense_download(fmx_ctx* ctx, uint32_t min_hits, double* xyz, uint64_t* scan, uint32_t* index,
                               uint32_t* hits, uint32_t* n);
-/* Empty the map; the integration counter restarts at 0. */
+/* Empty the map; the integration counter restarts at 0.  Forgets the rolling centre and
+ * leaves the spill alone (below). */
 fmx_status fmx_dense_clear(fmx_ctx* ctx);
+
+/* ---------------- rolling the dense voxel map ----------------------------------
+ * Bounded memory for an unbounded stream: the map keeps what lies in a box around a centre,
+ * everything else leaves the device and goes to the caller (DESIGN.md §Dense map, Rolling).
+ * A roll takes a centre c (three finite doubles) and half-extents half (three uint32, in
+ * voxels, each <= 2^21).  The centre voxel is cc_k = floor(c_k / voxel_width) in fp64, the
+ * integration's own expression; FMX_E_INVAL unless every |cc_k| < 2^20 - 1.  A stored
+ * voxel's coordinates v_k are decoded from its key; it is inside iff |v_k - cc_k| <= half_k
+ * on all three axes, in 64-bit integers.  Every voxel outside is evicted: its (xyz, scan_idx,
+ * index, hits), the fields fmx_dense_download returns, go to the caller in no particular
+ * order and the voxel leaves the table.  Every voxel inside stays, bit for bit.  Afterwards
+ * `voxels` is the number kept and the capacity rule uses it; the integration counter is
+ * unchanged; a later integration that sees an evicted voxel again opens it as a new voxel.
+ * The content after a roll does not depend on the order the device's threads run in.
+ * All of these: FMX_E_STATE unless the dense map is configured and enabled (fmx_roll_stats
+ * excepted); FMX_E_INVAL for a null centre, a non-finite centre, a centre voxel out of
+ * range or half_k > 2^21.  A context that calls none of them allocates and launches nothing
+ * for them. */
+typedef struct fmx_roll_params {
+  int32_t enable;     /* 0: the register path never rolls */
+  uint32_t half[3];   /* box half-extents in voxels */
+  double step;        /* metres, finite, >= 0 */
+  int32_t spill;      /* 1: keep evicted voxels for fmx_roll_drain; 0: discard them */
+} fmx_roll_params;
+/* Register path, opt-in (enable = 1): at the start of the registration of scan j >= 1, before
+ * it is decided whether scan j is integrated, let p be the translation of the pose
+ * fmx_current_pose returns at that moment (scan j - 1's final pose).  With no centre recorded,
+ * p is recorded and nothing rolls.  Otherwise the map rolls about p, and p is recorded, iff
+ * max_k |p_k - centre_k| >= step (fp64), or scan j is due by `every` and voxels + n >
+ * max_voxels.  A p whose centre voxel is out of range, or a failed allocation, skips the roll;
+ * neither fails the registration.  Evicted voxels go to the context's host spill, or nowhere
+ * when spill = 0.  Estimation is untouched.  May be called at any time once the map is on;
+ * forgets the recorded centre.  FMX_E_INVAL for a negative or non-finite step. */
+fmx_status fmx_roll_configure(fmx_ctx* ctx, const fmx_roll_params* p);
+/* out = {inside, outside} of the box; changes nothing. */
+fmx_status fmx_roll_count(fmx_ctx* ctx, const double centre[3], const uint32_t half[3], uint64_t out[2]);
+/* Stand-alone roll.  With any buffer non-NULL *n is the capacity on entry (FMX_E_SIZE if too
+ * small: the map and the buffers stay untouched) and the evicted count on return; buffers
+ * left NULL are skipped.  With all four NULL the evicted voxels are discarded; n may then be
+ * NULL, or receives the count.  FMX_E_OOM, nothing changed, when a device allocation fails. */
+fmx_status fmx_roll_evict(fmx_ctx* ctx, const double centre[3], const uint32_t half[3], double* xyz, uint64_t* scan,
+                          uint32_t* index, uint32_t* hits, uint32_t* n);
+/* The host spill of the register path's rolls, by fmx_dense_download's two-call protocol; a
+ * successful filling call empties it.  It holds scan_idx values: fmx_dense_clear does not
+ * invalidate it. */
+fmx_status fmx_roll_drain(fmx_ctx* ctx, double* xyz, uint64_t* scan, uint32_t* index, uint32_t* hits, uint32_t* n);
+/* out = {rolls, voxels evicted in total, voxels now in the spill, kept by the last roll,
+ * evicted by the last roll, index of the scan whose registration ran the last roll}: the
+ * register path's rolls only; all 0 when never used. */
+fmx_status fmx_roll_stats(fmx_ctx* ctx, uint64_t out[6]);
 
 /* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
  * pose at the middle of the last registered sweep. */
