@@ -1,7 +1,8 @@
 // densemap.hip — the opt-in dense voxel map of the registered scans (DESIGN.md §Dense map;
 // include/fmx/fmx.h, fmx_dense_integrate).  A fixed-capacity open-addressed hash of world
 // voxels, structure-of-arrays, 44 B per slot: keys (u64), tags (u64), hits (u32), xyz
-// (3 doubles).  An integration is two launches on one stream, no host round trip between
+// (3 doubles); 52 B once carving has been enabled (misses and seen, u32 each: the carve
+// block further down).  An integration is two launches on one stream, no host round trip between
 // them; the kernel boundary is the only ordering (no in-kernel device-scope fence: see
 // organize.hip's header for what one per wave costs on gfx950).
 //
@@ -182,35 +183,50 @@ __global__ __launch_bounds__(kDenseFillThreads) void k_dense_fill(const float4* 
   }
 }
 
-// Slots with hits >= min_hits: counted (out_n), one atomic per wave.
+// What a download takes: hits >= min_hits and, with den != 0, misses * den <= hits * num in
+// 64-bit integers (fmx_carve_download).  misses: the carve block's array, or null (reads 0).
+struct DenseTake {
+  uint32_t min_hits, num, den;
+  const uint32_t* misses;
+};
+__device__ __forceinline__ uint32_t dense_misses(const DenseTake& t, uint64_t s) { return t.misses ? t.misses[s] : 0u; }
+__device__ __forceinline__ bool dense_take(const DenseTake& t, uint32_t h, uint64_t s) {
+  if (h < t.min_hits) return false;
+  if (!t.den) return true;
+  return (unsigned long long)dense_misses(t, s) * t.den <= (unsigned long long)h * t.num;
+}
+
+// Slots a download takes: counted (out_n), one atomic per wave.
 __global__ __launch_bounds__(kDenseThreads) void k_dense_count(const uint32_t* __restrict__ hits, uint64_t slots,
-                                                               uint32_t min_hits, uint32_t* __restrict__ out_n) {
+                                                               DenseTake tk, uint32_t* __restrict__ out_n) {
   uint32_t mine = 0;
   for (uint64_t base = (uint64_t)blockIdx.x * kDenseThreads; base < slots; base += (uint64_t)gridDim.x * kDenseThreads) {
     const uint64_t s = base + threadIdx.x;
-    const bool take = s < slots && hits[s] >= min_hits;
+    const bool take = s < slots && dense_take(tk, hits[s], s);
     mine += (uint32_t)__popcll(__ballot(take));  // the same in every lane of the wave
   }
   if ((threadIdx.x & 63) == 0 && mine) atomicAdd(out_n, mine);
 }
 
-// ... appended: (xyz, tag, hits) of each, in no particular order; cap: the room in the outputs.
+// ... appended: (xyz, tag, hits, and misses when o_miss is given) of each, in no particular
+// order; cap: the room in the outputs.
 // Each wave walks its slots twice: once to count what it will take, then ONE atomic for its
 // place in the output, then again to copy (an atomic per wave and step, one word for all:
 // 4.0 ms for 430k voxels in 2^26 slots at C4, profiles/dense_cost.json has this form's time).
 __global__ __launch_bounds__(kDenseThreads) void k_dense_compact(const uint32_t* __restrict__ hits,
                                                                  const unsigned long long* __restrict__ tags,
                                                                  const double* __restrict__ xyz, uint64_t slots,
-                                                                 uint32_t min_hits, uint32_t cap,
+                                                                 DenseTake tk, uint32_t cap,
                                                                  uint32_t* __restrict__ out_n, double* __restrict__ o_xyz,
                                                                  unsigned long long* __restrict__ o_tag,
-                                                                 uint32_t* __restrict__ o_hits) {
+                                                                 uint32_t* __restrict__ o_hits,
+                                                                 uint32_t* __restrict__ o_miss) {
   const int lane = threadIdx.x & 63;
   const uint64_t first = (uint64_t)blockIdx.x * kDenseThreads, step = (uint64_t)gridDim.x * kDenseThreads;
   uint32_t mine = 0;
   for (uint64_t base = first; base < slots; base += step) {
     const uint64_t s = base + threadIdx.x;
-    mine += (uint32_t)__popcll(__ballot(s < slots && hits[s] >= min_hits));  // the same in every lane of the wave
+    mine += (uint32_t)__popcll(__ballot(s < slots && dense_take(tk, hits[s], s)));  // the same in every lane of the wave
   }
   if (!mine) return;  // (the whole wave)
   uint32_t at = 0;
@@ -219,7 +235,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_dense_compact(const uint32_t*
   for (uint64_t base = first; base < slots; base += step) {
     const uint64_t s = base + threadIdx.x;
     const uint32_t h = s < slots ? hits[s] : 0u;
-    const bool take = s < slots && h >= min_hits;
+    const bool take = s < slots && dense_take(tk, h, s);
     const unsigned long long b = __ballot(take);
     if (take) {
       const uint32_t o = at + (uint32_t)__popcll(b & lanemask_lt());
@@ -229,6 +245,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_dense_compact(const uint32_t*
         o_xyz[3 * (size_t)o + 2] = xyz[3 * s + 2];
         o_tag[o] = tags[s];
         o_hits[o] = h;
+        if (o_miss) o_miss[o] = dense_misses(tk, s);
       }
     }
     at += (uint32_t)__popcll(b);
@@ -249,6 +266,10 @@ __global__ __launch_bounds__(kDenseThreads) void k_dense_compact(const uint32_t*
 //             this launch, so the table is empty when the launch ends, without a memset.
 //   reinsert  one lane per kept voxel: the claim's probe with its own (distinct) key, then
 //             plain stores of tag, hits and point; sets the device's voxel total.
+//
+// With carving enabled a voxel's miss count travels with it (both streams) and the slot it
+// leaves is zeroed in misses and seen: seen is nonzero only in occupied slots, so a roll
+// leaves it all zero (a kept voxel's new slot has no mark from the integration before).
 //
 // A voxel is inside iff |v_k - cc_k| <= half_k on every axis, v decoded from the key, in
 // 64-bit integers (tests/roll_ref.py restates it).
@@ -285,13 +306,15 @@ __global__ __launch_bounds__(kDenseThreads) void k_roll_count(const unsigned lon
   }
 }
 
-// cur: {evicted, kept} cursors; cap_e / cap_k: the room in the outputs (e_*) and the staging list (s_*)
+// cur: {evicted, kept} cursors; cap_e / cap_k: the room in the outputs (e_*) and the staging list (s_*);
+// misses, seen, e_miss, s_miss: all null unless carving has been enabled
 __global__ __launch_bounds__(kDenseThreads) void k_roll_split(
     unsigned long long* keys, unsigned long long* tags, uint32_t* hits, const double* __restrict__ xyz, uint64_t slots,
     RollBox box, uint32_t cap_e, uint32_t cap_k, uint32_t* __restrict__ cur,
     double* __restrict__ e_xyz, unsigned long long* __restrict__ e_tag, uint32_t* __restrict__ e_hits,
     unsigned long long* __restrict__ s_key, unsigned long long* __restrict__ s_tag, uint32_t* __restrict__ s_hits,
-    double* __restrict__ s_xyz) {
+    double* __restrict__ s_xyz, uint32_t* misses, uint32_t* seen, uint32_t* __restrict__ e_miss,
+    uint32_t* __restrict__ s_miss) {
   const int lane = threadIdx.x & 63;
   const uint64_t first = (uint64_t)blockIdx.x * kDenseThreads, step = (uint64_t)gridDim.x * kDenseThreads;
   uint32_t n_e = 0, n_k = 0;
@@ -318,6 +341,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_roll_split(
     if (occ) {
       const unsigned long long t = tags[s];
       const uint32_t h = hits[s];
+      const uint32_t ms = misses ? misses[s] : 0u;
       const double x = xyz[3 * s + 0], y = xyz[3 * s + 1], z = xyz[3 * s + 2];
       if (in) {
         const uint32_t o = at_k + (uint32_t)__popcll(b_k & lanemask_lt());
@@ -325,6 +349,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_roll_split(
           s_key[o] = k;
           s_tag[o] = t;
           s_hits[o] = h;
+          if (s_miss) s_miss[o] = ms;
           s_xyz[3 * (size_t)o + 0] = x;
           s_xyz[3 * (size_t)o + 1] = y;
           s_xyz[3 * (size_t)o + 2] = z;
@@ -334,6 +359,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_roll_split(
         if (o < cap_e) {
           e_tag[o] = t;
           e_hits[o] = h;
+          if (e_miss) e_miss[o] = ms;
           e_xyz[3 * (size_t)o + 0] = x;
           e_xyz[3 * (size_t)o + 1] = y;
           e_xyz[3 * (size_t)o + 2] = z;
@@ -342,6 +368,10 @@ __global__ __launch_bounds__(kDenseThreads) void k_roll_split(
       keys[s] = kDenseEmpty;
       tags[s] = ~0ull;
       hits[s] = 0u;
+      if (misses) {
+        misses[s] = 0u;
+        seen[s] = 0u;
+      }
     }
     at_k += (uint32_t)__popcll(b_k);
     at_e += (uint32_t)__popcll(b_e);
@@ -353,7 +383,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_roll_reinsert(
     const unsigned long long* __restrict__ s_key, const unsigned long long* __restrict__ s_tag,
     const uint32_t* __restrict__ s_hits, const double* __restrict__ s_xyz, uint32_t kept, unsigned long long* keys,
     unsigned long long* __restrict__ tags, uint32_t* __restrict__ hits, double* __restrict__ xyz, uint32_t slot_mask,
-    uint32_t* __restrict__ cnt) {
+    uint32_t* __restrict__ cnt, const uint32_t* __restrict__ s_miss, uint32_t* __restrict__ misses) {
   const uint32_t i = blockIdx.x * (uint32_t)kDenseThreads + threadIdx.x;
   if (i == 0) cnt[3] = kept;
   if (i >= kept) return;
@@ -367,12 +397,186 @@ __global__ __launch_bounds__(kDenseThreads) void k_roll_reinsert(
     if (k == kDenseEmpty) {
       tags[h] = s_tag[i];
       hits[h] = s_hits[i];
+      if (misses) misses[h] = s_miss[i];
       xyz[3 * (size_t)h + 0] = s_xyz[3 * (size_t)i + 0];
       xyz[3 * (size_t)h + 1] = s_xyz[3 * (size_t)i + 1];
       xyz[3 * (size_t)h + 2] = s_xyz[3 * (size_t)i + 2];
       return;
     }
     h = (h + 1) & slot_mask;
+  }
+}
+
+// ---- carving (DESIGN.md §Dense map, Carving; include/fmx/fmx.h, fmx_carve_configure).  A
+// return at range r proves the segment from the sensor to it empty at that moment: every
+// point that the integration took also casts a ray through the table, and a stored voxel
+// counts the rays that passed through it (misses).  Two more u32 per slot, allocated when
+// carving is first enabled: misses, and seen = (the number of the last integration that put
+// a point into the slot) + 1.  After an integration's claim and fill, on the same stream, the
+// kernel boundary again the only ordering:
+//
+//   mark    one lane per point: seen[slot_of[i]] = seq + 1, a plain store (every writer of a
+//           slot writes the same value).
+//   rays    one lane per ray (adjacent columns of an organized scan have similar lengths):
+//           the voxel walk of the header, one fp64 division per step (tau_k changes only
+//           when cur_k does), and per examined voxel a find-only probe of the table: the key
+//           word (8 B), and when it is there the seen word (4) and, unless that exempts the
+//           voxel, one return-less atomicAdd on misses (4).  The walk is bound by those
+//           dependent random loads, not by bytes; what hides them is waves in flight, so the
+//           walk's state stays in registers (no dynamically indexed array).
+//
+// The launch's counters: rays rides in the ticket word as the fill's count does; steps,
+// misses and exempt are 64-bit, so each wave adds its sums with one atomic per counter and
+// WAITS for them (returning atomics: they have been performed when the wave goes on) before
+// the block's barrier, and the block's ticket follows the barrier.  The block that finds
+// every ticket in therefore finds every sum in, reads them with device-scope loads,
+// publishes and re-arms.  The barrier also stands behind every lane's read of its point.
+//
+// The result does not depend on the order the lanes run in: the set of (ray, voxel) pairs is
+// fixed by the definition, keys and seen do not change during the launch, misses is a sum.
+//
+// Look-ahead: a lane's walk is one dependent chain only in its arithmetic; which voxels it
+// examines does not depend on what the lookups return.  So the lane walks FMX_CARVE_AHEAD
+// voxels, issues their home-slot loads back to back, and only then looks at what came back
+// (a chain past the home slot is then followed load by load).  FMX_CARVE_AHEAD=1 builds the
+// plain form, one load in flight per lane: about 1.4x this form's time per C4 carve at
+// 0.2 m voxels, same box, alternated; 8 is within 2 % of 4 and costs 24 more registers per
+// lane (profiles/carve_ahead_ab.json).  Sharing one atomic among lanes that examine the same
+// voxel, as the claim's in-wave merge does, was not built: in that workload about 2 % of the
+// examined voxels are present at all and under 1 % take an atomic (profiles/carve_cost.json).
+#ifndef FMX_CARVE_AHEAD
+#define FMX_CARVE_AHEAD 4
+#endif
+struct CarveArgs {
+  double max2;
+  uint32_t margin, stride;
+  uint32_t exempt;  // seq + 1 of the integration whose voxels are exempt; 0: none are
+};
+
+__global__ __launch_bounds__(kDenseThreads) void k_carve_mark(const uint32_t* __restrict__ slot_of, uint32_t n,
+                                                              uint32_t mark, uint32_t* __restrict__ seen) {
+  const uint32_t i = blockIdx.x * (uint32_t)kDenseThreads + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t slot = slot_of[i];
+  if (slot != kDenseDropped) seen[slot] = mark;
+}
+
+__device__ __forceinline__ unsigned long long carve_add_wait(unsigned long long* p, unsigned long long v) {
+  const unsigned long long r = __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::"v"(r) : "memory");  // the value is back: the add has been performed
+  return r;
+}
+
+// Find only, from the home slot h whose key word k is already here (bounded by the table: the
+// load is at most 1/2, a chain meets an empty slot).  0 absent, 1 a miss counted, 2 exempt.
+__device__ __forceinline__ int carve_find(unsigned long long key, uint32_t h, unsigned long long k,
+                                          const unsigned long long* __restrict__ keys, uint32_t slot_mask, uint32_t exempt,
+                                          const uint32_t* __restrict__ seen, uint32_t* misses) {
+  for (uint32_t probe = 0; probe <= slot_mask; ++probe) {
+    if (k == key) {
+      if (exempt && seen[h] == exempt) return 2;
+      atomicAdd(&misses[h], 1u);  // result unused: return-less
+      return 1;
+    }
+    if (k == kDenseEmpty) return 0;
+    h = (h + 1) & slot_mask;
+    k = keys[h];
+  }
+  return 0;
+}
+
+// cnt: {-, steps, misses, exempt, ticket << 32 | rays}; res (pinned, device-visible): {rays,
+// steps, misses, exempt}; flag: the completion word, seq_flag its value for this launch
+__global__ __launch_bounds__(kDenseThreads) void k_carve_rays(const float4* __restrict__ pts, uint32_t n, DenseArgs a,
+                                                              CarveArgs cv, const unsigned long long* __restrict__ keys,
+                                                              const uint32_t* __restrict__ seen, uint32_t* misses,
+                                                              unsigned long long* cnt, unsigned long long* __restrict__ res,
+                                                              uint32_t* flag, uint32_t seq_flag) {
+  const uint32_t i = blockIdx.x * (uint32_t)kDenseThreads + threadIdx.x;
+  const double inf = __longlong_as_double(0x7FF0000000000000ll);
+  bool ray = false;
+  uint32_t nex = 0;  // voxels to examine
+  int c0 = 0, c1 = 0, c2 = 0, b0 = 0, b1 = 0, b2 = 0, s0 = 0, s1 = 0, s2 = 0;
+  double o0 = 0.0, o1 = 0.0, o2 = 0.0, d0 = 0.0, d1 = 0.0, d2 = 0.0, t0 = inf, t1 = inf, t2 = inf;
+  if (i < n && i % cv.stride == 0) {
+    const float4 p = pts[i];
+    unsigned long long pkey = 0;
+    if (dense_classify(p, a, &pkey) == 0 && (double)((p.x * p.x + p.y * p.y) + p.z * p.z) < cv.max2) {
+      ray = true;
+      double e[3];
+      d_xform(a.T.m, (double)p.x, (double)p.y, (double)p.z, e);
+      o0 = a.T.m[3], o1 = a.T.m[7], o2 = a.T.m[11];
+      // (both in range: the host checked a, the classification b; |c| < 2^20 fits an int)
+      c0 = (int)floor(o0 / a.w), c1 = (int)floor(o1 / a.w), c2 = (int)floor(o2 / a.w);
+      b0 = (int)floor(e[0] / a.w), b1 = (int)floor(e[1] / a.w), b2 = (int)floor(e[2] / a.w);
+      d0 = e[0] - o0, d1 = e[1] - o1, d2 = e[2] - o2;
+      s0 = b0 > c0 ? 1 : -1, s1 = b1 > c1 ? 1 : -1, s2 = b2 > c2 ? 1 : -1;
+      const uint32_t S = (uint32_t)abs(b0 - c0) + (uint32_t)abs(b1 - c1) + (uint32_t)abs(b2 - c2);
+      nex = S > cv.margin ? S - cv.margin : 0u;
+      if (c0 != b0) t0 = ((double)(c0 + (s0 > 0 ? 1 : 0)) * a.w - o0) / d0;
+      if (c1 != b1) t1 = ((double)(c1 + (s1 > 0 ? 1 : 0)) * a.w - o1) / d1;
+      if (c2 != b2) t2 = ((double)(c2 + (s2 > 0 ? 1 : 0)) * a.w - o2) / d2;
+    }
+  }
+  uint32_t n_miss = 0, n_ex = 0;
+  for (uint32_t s = 0; s < nex; s += (uint32_t)FMX_CARVE_AHEAD) {
+    // The path does not depend on what the table holds: walk FMX_CARVE_AHEAD voxels first and
+    // issue their home-slot loads together, so that many misses are in flight per lane.
+    unsigned long long key[FMX_CARVE_AHEAD], k0[FMX_CARVE_AHEAD];
+    uint32_t h0[FMX_CARVE_AHEAD];
+#pragma unroll
+    for (int u = 0; u < FMX_CARVE_AHEAD; ++u) {
+      // (cur stays in the box between a and b, so each coordinate + bias is a 21-bit field)
+      key[u] = ((unsigned long long)((long long)c0 + kDenseBias) << 42) |
+               ((unsigned long long)((long long)c1 + kDenseBias) << 21) | (unsigned long long)((long long)c2 + kDenseBias);
+      h0[u] = (uint32_t)mix64(key[u]) & a.slot_mask;
+      k0[u] = s + (uint32_t)u < nex ? keys[h0[u]] : kDenseEmpty;  // (past the last examined voxel: nothing to find)
+      // the axis with the smallest tau, the lowest among equal ones; only its tau changes
+      if (t0 <= t1 && t0 <= t2) {
+        c0 += s0;
+        t0 = c0 != b0 ? ((double)(c0 + (s0 > 0 ? 1 : 0)) * a.w - o0) / d0 : inf;
+      } else if (t1 <= t2) {
+        c1 += s1;
+        t1 = c1 != b1 ? ((double)(c1 + (s1 > 0 ? 1 : 0)) * a.w - o1) / d1 : inf;
+      } else {
+        c2 += s2;
+        t2 = c2 != b2 ? ((double)(c2 + (s2 > 0 ? 1 : 0)) * a.w - o2) / d2 : inf;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < FMX_CARVE_AHEAD; ++u) {
+      const int hit = carve_find(key[u], h0[u], k0[u], keys, a.slot_mask, cv.exempt, seen, misses);
+      n_miss += hit == 1 ? 1u : 0u;
+      n_ex += hit == 2 ? 1u : 0u;
+    }
+  }
+  // (per wave: at most 64 * 3 * 2^21 steps, so the 32-bit sums cannot wrap)
+  const uint32_t w_rays = (uint32_t)__popcll(__ballot(ray));
+  const uint32_t w_steps = wave_sum(nex), w_miss = wave_sum(n_miss), w_ex = wave_sum(n_ex);
+  if ((threadIdx.x & 63) == 0) {
+    if (w_steps) carve_add_wait(&cnt[1], w_steps);
+    if (w_miss) carve_add_wait(&cnt[2], w_miss);
+    if (w_ex) carve_add_wait(&cnt[3], w_ex);
+  }
+  __shared__ uint32_t sh_rays[kDenseThreads / 64];
+  if ((threadIdx.x & 63) == 0) sh_rays[threadIdx.x >> 6] = w_rays;
+  // (every lane's read of pts has returned, and every wave's sums are in, by this barrier)
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  uint32_t b_rays = 0;
+  for (int wv = 0; wv < kDenseThreads / 64; ++wv) b_rays += sh_rays[wv];
+  const unsigned long long mine = (1ull << 32) | (unsigned long long)b_rays;
+  const unsigned long long all = atomicAdd(&cnt[4], mine) + mine;
+  if ((uint32_t)(all >> 32) == gridDim.x) {  // every other block's ticket, so its sums too, are in
+    const unsigned long long steps = __hip_atomic_load(&cnt[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long miss = __hip_atomic_load(&cnt[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long ex = __hip_atomic_load(&cnt[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    cnt[1] = cnt[2] = cnt[3] = cnt[4] = 0;
+    host_store(&res[0], (unsigned long long)(uint32_t)all);
+    host_store(&res[1], steps);
+    host_store(&res[2], miss);
+    host_store(&res[3], ex);
+    publish_flag(flag, seq_flag);
   }
 }
 
@@ -416,14 +620,50 @@ void run_dense_integrate(fmx_ctx* c, const float4* d_pts, size_t n, const double
   }
 }
 
-// The number of voxels with hits >= min_hits into c->dense.h_n[0] (one launch; waits).
-uint32_t run_dense_count(fmx_ctx* c, uint32_t min_hits, hipStream_t st) {
+// Mark (mark != 0: c->dense.slot_of holds the claim of these same n points) + rays of the n > 0
+// points at d_pts from pose34's translation, on stream st.  The counts and the completion
+// word (flag_seq, the low half of c->dense.carve.h_res[5]) land in c->dense.carve.h_res once
+// the last block of the rays is through.
+void run_carve(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, uint32_t mark, uint32_t flag_seq,
+               hipStream_t st) {
   auto& D = c->dense;
+  auto& Cv = D.carve;
+  const DenseArgs a = dense_args(c, pose34);
+  const CarveArgs cv{Cv.cfg.max2, Cv.cfg.margin, Cv.cfg.stride, mark};
+  const uint32_t blocks = (uint32_t)((n + kDenseThreads - 1) / kDenseThreads);
+  if (mark) {
+    // the slot word and the mark (4 + 4 per point)
+    ProfScope ps(c->prof, PROF_CARVE, (double)n * 8.0, st);
+    hipLaunchKernelGGL(k_carve_mark, dim3(blocks), dim3(kDenseThreads), 0, st, D.slot_of.p, (uint32_t)n, mark, Cv.seen.p);
+    FMX_HIP(hipGetLastError());
+  }
+  {
+    // the points on the stride (16 each); the walk's 8 B per step, + 4 + 4 where the voxel
+    // is present, are not known at launch and not counted (DESIGN.md has the model, the
+    // launch's own counts give the steps)
+    ProfScope ps(c->prof, PROF_CARVE, (double)((n + Cv.cfg.stride - 1) / Cv.cfg.stride) * 16.0, st);
+    hipLaunchKernelGGL(k_carve_rays, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)n, a, cv, D.keys.p,
+                       Cv.seen.p, Cv.misses.p, Cv.cnt.p, Cv.h_res.d, reinterpret_cast<uint32_t*>(Cv.h_res.d + 5), flag_seq);
+    FMX_HIP(hipGetLastError());
+  }
+}
+
+// The miss filter of a download; the miss array only where it exists and the filter reads it.
+static DenseTake dense_take_args(const fmx_ctx* c, uint32_t min_hits, uint32_t num, uint32_t den, bool with_misses) {
+  const auto& Cv = c->dense.carve;
+  return DenseTake{min_hits, num, den, Cv.have && (den || with_misses) ? Cv.misses.p : nullptr};
+}
+
+// The number of voxels a download takes into c->dense.h_n[0] (one launch; waits).
+uint32_t run_dense_count(fmx_ctx* c, uint32_t min_hits, uint32_t miss_num, uint32_t miss_den, hipStream_t st) {
+  auto& D = c->dense;
+  const DenseTake tk = dense_take_args(c, min_hits, miss_num, miss_den, false);
   FMX_HIP(hipMemsetAsync(D.out_n.p, 0, sizeof(uint32_t), st));
   {
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (D.slots + kDenseThreads - 1) / kDenseThreads);
-    ProfScope ps(c->prof, PROF_DENSE, (double)D.slots * 4.0, st);  // every slot's hit count
-    hipLaunchKernelGGL(k_dense_count, dim3(blocks), dim3(kDenseThreads), 0, st, D.hits.p, D.slots, min_hits, D.out_n.p);
+    // every slot's hit count (+ its miss count under a miss filter; short-circuits not counted)
+    ProfScope ps(c->prof, PROF_DENSE, (double)D.slots * (tk.misses ? 8.0 : 4.0), st);
+    hipLaunchKernelGGL(k_dense_count, dim3(blocks), dim3(kDenseThreads), 0, st, D.hits.p, D.slots, tk, D.out_n.p);
     FMX_HIP(hipGetLastError());
   }
   FMX_HIP(hipMemcpyAsync(D.h_n.p, D.out_n.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -431,29 +671,40 @@ uint32_t run_dense_count(fmx_ctx* c, uint32_t min_hits, hipStream_t st) {
   return D.h_n.p[0];
 }
 
-// Those count voxels appended to c->dense.o_xyz / o_tag / o_hits (one launch; queued only).
-void run_dense_compact(fmx_ctx* c, uint32_t min_hits, uint32_t count, hipStream_t st) {
+// Those count voxels appended to c->dense.o_xyz / o_tag / o_hits (and carve.o_miss, sized by
+// the caller, with with_misses on a map that has the array) (one launch; queued only).
+void run_dense_compact(fmx_ctx* c, uint32_t min_hits, uint32_t miss_num, uint32_t miss_den, bool with_misses,
+                       uint32_t count, hipStream_t st) {
   auto& D = c->dense;
   D.o_xyz.ensure(3 * (size_t)count);
   D.o_tag.ensure(count);
   D.o_hits.ensure(count);
+  const DenseTake tk = dense_take_args(c, min_hits, miss_num, miss_den, with_misses);
+  uint32_t* o_miss = with_misses && D.carve.have ? D.carve.o_miss.p : nullptr;
   FMX_HIP(hipMemsetAsync(D.out_n.p, 0, sizeof(uint32_t), st));
   const uint32_t blocks = (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (D.slots + kDenseThreads - 1) / kDenseThreads);
   // every slot's hit count, twice (2 * 4) + per voxel taken its tag and point read and
-  // written, its hit count written (2 * (8 + 24) + 4)
-  ProfScope ps(c->prof, PROF_DENSE, (double)D.slots * 8.0 + (double)count * 68.0, st);
+  // written, its hit count written (2 * (8 + 24) + 4); with the miss array in play each
+  // slot's miss count twice more (2 * 4) and a taken voxel's written (4)
+  ProfScope ps(c->prof, PROF_DENSE,
+               (double)D.slots * (tk.misses ? 16.0 : 8.0) + (double)count * (o_miss ? 72.0 : 68.0), st);
   hipLaunchKernelGGL(k_dense_compact, dim3(blocks), dim3(kDenseThreads), 0, st, D.hits.p, D.tags.p, D.xyz.p, D.slots,
-                     min_hits, count, D.out_n.p, D.o_xyz.p, D.o_tag.p, D.o_hits.p);
+                     tk, count, D.out_n.p, D.o_xyz.p, D.o_tag.p, D.o_hits.p, o_miss);
   FMX_HIP(hipGetLastError());
 }
 
-// Keys and tags to all-ones, hits and the counters to 0, on stream st.
+// Keys and tags to all-ones, hits and the counters (and, where they exist, misses and seen) to
+// 0, on stream st.
 void run_dense_clear(fmx_ctx* c, hipStream_t st) {
   auto& D = c->dense;
   FMX_HIP(hipMemsetAsync(D.keys.p, 0xFF, D.slots * sizeof(unsigned long long), st));
   FMX_HIP(hipMemsetAsync(D.tags.p, 0xFF, D.slots * sizeof(unsigned long long), st));
   FMX_HIP(hipMemsetAsync(D.hits.p, 0, D.slots * sizeof(uint32_t), st));
   FMX_HIP(hipMemsetAsync(D.cnt.p, 0, 8 * sizeof(uint32_t), st));
+  if (D.carve.have) {
+    FMX_HIP(hipMemsetAsync(D.carve.misses.p, 0, D.slots * sizeof(uint32_t), st));
+    FMX_HIP(hipMemsetAsync(D.carve.seen.p, 0, D.slots * sizeof(uint32_t), st));
+  }
 }
 
 static RollBox roll_box(const long long cc[3], const uint32_t half[3]) {
@@ -486,27 +737,34 @@ void run_roll_count(fmx_ctx* c, const long long cc[3], const uint32_t half[3], u
 
 // After run_roll_count of the same box (its cursors are still zero; the outputs and the
 // staging list hold evicted / kept entries): the evicted voxels appended to c->dense.o_xyz /
-// o_tag / o_hits, the kept ones put back, the device's voxel total set (queued only).
+// o_tag / o_hits, the kept ones put back, the device's voxel total set (queued only).  On a
+// map with the carve arrays the miss counts go along (carve.o_miss / s_miss, sized by the caller).
 void run_roll_rebuild(fmx_ctx* c, const long long cc[3], const uint32_t half[3], uint32_t kept, uint32_t evicted,
                       hipStream_t st) {
   auto& D = c->dense;
   auto& Rl = D.roll;
+  auto& Cv = D.carve;
+  const double mb = Cv.have ? 1.0 : 0.0;  // (the miss word wherever the hit word goes; seen zeroed)
   {
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (D.slots + kDenseThreads - 1) / kDenseThreads);
     // every slot's key, twice (2 * 8) + per evicted voxel its tag, hits and point read and
     // written, its slot emptied (2 * 36 + 20) + per kept voxel the same and its key written (+ 8)
-    ProfScope ps(c->prof, PROF_DENSE, (double)D.slots * 16.0 + (double)evicted * 92.0 + (double)kept * 100.0, st);
+    ProfScope ps(c->prof, PROF_DENSE,
+                 (double)D.slots * 16.0 + (double)evicted * (92.0 + 16.0 * mb) + (double)kept * (100.0 + 16.0 * mb), st);
     hipLaunchKernelGGL(k_roll_split, dim3(blocks), dim3(kDenseThreads), 0, st, D.keys.p, D.tags.p, D.hits.p, D.xyz.p,
                        D.slots, roll_box(cc, half), evicted, kept, Rl.n.p + 2, D.o_xyz.p, D.o_tag.p, D.o_hits.p, Rl.s_key.p,
-                       Rl.s_tag.p, Rl.s_hits.p, Rl.s_xyz.p);
+                       Rl.s_tag.p, Rl.s_hits.p, Rl.s_xyz.p, Cv.have ? Cv.misses.p : nullptr,
+                       Cv.have ? Cv.seen.p : nullptr, Cv.have ? Cv.o_miss.p : nullptr,
+                       Cv.have && kept ? Cv.s_miss.p : nullptr);
     FMX_HIP(hipGetLastError());
   }
   if (kept) {
     const uint32_t blocks = (kept + kDenseThreads - 1) / kDenseThreads;
     // the staged voxel read (44) and written: key, tag, hits, point (44); probes past the home slot not counted
-    ProfScope ps(c->prof, PROF_DENSE, (double)kept * 88.0, st);
+    ProfScope ps(c->prof, PROF_DENSE, (double)kept * (88.0 + 8.0 * mb), st);
     hipLaunchKernelGGL(k_roll_reinsert, dim3(blocks), dim3(kDenseThreads), 0, st, Rl.s_key.p, Rl.s_tag.p, Rl.s_hits.p,
-                       Rl.s_xyz.p, kept, D.keys.p, D.tags.p, D.hits.p, D.xyz.p, (uint32_t)(D.slots - 1), D.cnt.p);
+                       Rl.s_xyz.p, kept, D.keys.p, D.tags.p, D.hits.p, D.xyz.p, (uint32_t)(D.slots - 1), D.cnt.p,
+                       Cv.have ? Cv.s_miss.p : nullptr, Cv.have ? Cv.misses.p : nullptr);
     FMX_HIP(hipGetLastError());
   } else {
     FMX_HIP(hipMemsetAsync(D.cnt.p + 3, 0, sizeof(uint32_t), st));

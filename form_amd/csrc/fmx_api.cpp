@@ -67,7 +67,7 @@ void match_counts_fetch(fmx_ctx* c, bool wait) {
 static const char* kProfNames[PROF_COUNT] = {"extract_rows", "closest",   "fit",       "compact", "map_build",
                                              "match",        "pair_sort", "linearize", "insert",  "window",
                                              "match_linearize", "unpack", "moments", "deskew",
-                                             "organize", "dense"};
+                                             "organize", "dense", "carve"};
 
 ProfScope::ProfScope(Prof& p, int i, double by, hipStream_t s) : pr(p), id(i), bytes(by), st(s) {
   if (!pr.on) return;
@@ -1377,6 +1377,12 @@ void dense_release(fmx_ctx* c) {
   D.tags.release();
   D.hits.release();
   D.xyz.release();
+  D.carve.misses.release();  // (the carve arrays belong to the table they were sized for)
+  D.carve.seen.release();
+  D.carve.have = false;
+  D.carve.cfg = CarveCfg{};
+  D.carve.last = fmx_carve_counts{};
+  D.carve.last_carved = 0;
   D.max_voxels = D.slots = D.voxels = 0;
   D.seq_scan.clear();
   D.roll.on = D.roll.have_centre = false;  // (a roll configuration belongs to the map it was made for)
@@ -1384,19 +1390,41 @@ void dense_release(fmx_ctx* c) {
 // Queue the integration of the n device points at d (the capacity rule checked by the
 // caller) on the context stream; returns the completion word's value to wait for, 0 when
 // nothing was launched (n = 0: an integration that counts nothing).
+// With carving on and this integration's number a multiple of its `every`, the mark and the
+// rays follow on the same stream (none when the origin's voxel is out of range, or n = 0: a
+// carve that casts no ray).
 uint32_t dense_queue(fmx_ctx* c, const float4* d, size_t n, const double* pose34, uint64_t scan_idx) {
   auto& D = c->dense;
+  auto& Cv = D.carve;
   D.used = true;
   uint32_t flag = 0;
+  const uint32_t seq = (uint32_t)D.seq_scan.size();
+  Cv.last = fmx_carve_counts{};
+  Cv.last_carved = Cv.have && Cv.cfg.on && seq % Cv.cfg.every == 0 ? 1 : 0;
   if (n) {
     flag = D.flag_seq + 1;
-    run_dense_integrate(c, d, n, pose34, (uint32_t)D.seq_scan.size(), flag, c->stream);
+    run_dense_integrate(c, d, n, pose34, seq, flag, c->stream);
     D.flag_seq = D.pending = flag;
+    if (Cv.last_carved && carve_origin_ok(pose34, D.voxel_w)) {
+      run_carve(c, d, n, pose34, seq + 1, Cv.flag_seq + 1, c->stream);
+      Cv.flag_seq = Cv.pending = Cv.flag_seq + 1;
+    }
   } else {
     std::memset(D.h_res.p, 0, 5 * sizeof(uint32_t));
   }
   D.seq_scan.push_back(scan_idx);
   return flag;
+}
+// A queued carve: wait for its completion word (the rays have then read the scan), take the counts.
+void carve_finish(fmx_ctx* c, fmx_carve_counts* out) {
+  auto& Cv = c->dense.carve;
+  if (!Cv.pending) return;
+  wait_flag(c, reinterpret_cast<const volatile uint32_t*>(Cv.h_res.p + 5), Cv.pending, c->stream);
+  Cv.pending = 0;
+  if (out) {
+    const unsigned long long* h = Cv.h_res.p;
+    *out = fmx_carve_counts{(uint32_t)h[0], h[1], h[2], h[3]};
+  }
 }
 // Wait for it (the fill's last block has then seen every block's ticket: the scan is read),
 // take the new voxel total and the counts.
@@ -1411,12 +1439,14 @@ void dense_finish(fmx_ctx* c, uint32_t flag, fmx_dense_counts* out) {
     const uint32_t* h = D.h_res.p;
     *out = fmx_dense_counts{h[0], h[1], h[2], h[3], h[4]};
   }
+  carve_finish(c, &D.carve.last);  // the rays behind it: they have read the scan too
 }
 
 // An integration whose wait never ran (the call that queued it failed in between): its
 // voxel total is taken before anything reads or relies on the host's copy.
 void dense_settle(fmx_ctx* c) {
   if (c->dense.pending) dense_finish(c, c->dense.pending, nullptr);
+  carve_finish(c, &c->dense.carve.last);
 }
 
 // ---- rolling (fmx_roll_*; densemap.hip)
@@ -1452,12 +1482,24 @@ void roll_rebuild(fmx_ctx* c, const long long cc[3], const uint32_t half[3], uin
     roll_ensure(D.roll.s_hits, kept);
     roll_ensure(D.roll.s_xyz, 3 * (size_t)kept);
   }
+  if (D.carve.have) {  // the miss counts travel with the voxels
+    roll_ensure(D.carve.o_miss, evicted);
+    if (kept) roll_ensure(D.carve.s_miss, kept);
+  }
   run_roll_rebuild(c, cc, half, kept, evicted, c->stream);
   D.voxels = kept;
 }
 // The evicted voxels of the last roll_rebuild to the host (any pointer may be null); waits.
-void roll_fetch(fmx_ctx* c, uint32_t count, double* xyz, uint64_t* scan, uint32_t* index, uint32_t* hits) {
+// misses reads 0 on a map that never enabled carving.
+void roll_fetch(fmx_ctx* c, uint32_t count, double* xyz, uint64_t* scan, uint32_t* index, uint32_t* hits,
+                uint32_t* misses) {
   auto& D = c->dense;
+  if (misses) {
+    if (D.carve.have)
+      FMX_HIP(hipMemcpyAsync(misses, D.carve.o_miss.p, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    else
+      std::memset(misses, 0, (size_t)count * sizeof(uint32_t));
+  }
   std::vector<unsigned long long> tag;
   if (scan || index) {
     tag.resize(count);
@@ -1492,14 +1534,8 @@ void roll_on_register(fmx_ctx* c, uint64_t j, const double p[3], bool due, size_
   run_roll_count(c, cc, Rl.half, io, c->stream);
   const uint32_t kept = io[0], evicted = io[1];
   if (evicted) {
-    const size_t at = Rl.sp_scan.size();
     try {
-      if (Rl.spill) {
-        Rl.sp_xyz.reserve(3 * (at + evicted));
-        Rl.sp_scan.reserve(at + evicted);
-        Rl.sp_index.reserve(at + evicted);
-        Rl.sp_hits.reserve(at + evicted);
-      }
+      if (Rl.spill) Rl.sp.reserve(evicted);
       roll_rebuild(c, cc, Rl.half, kept, evicted);
     } catch (const std::bad_alloc&) {
       return;
@@ -1508,12 +1544,9 @@ void roll_on_register(fmx_ctx* c, uint64_t j, const double p[3], bool due, size_
       throw;
     }
     if (Rl.spill) {
-      Rl.sp_xyz.resize(3 * (at + evicted));  // within the reserved room: no allocation
-      Rl.sp_scan.resize(at + evicted);
-      Rl.sp_index.resize(at + evicted);
-      Rl.sp_hits.resize(at + evicted);
-      roll_fetch(c, evicted, Rl.sp_xyz.data() + 3 * at, Rl.sp_scan.data() + at, Rl.sp_index.data() + at,
-                 Rl.sp_hits.data() + at);
+      const size_t at = Rl.sp.grow(evicted);  // within the reserved room: no allocation
+      roll_fetch(c, evicted, Rl.sp.xyz.data() + 3 * at, Rl.sp.scan.data() + at, Rl.sp.index.data() + at,
+                 Rl.sp.hits.data() + at, Rl.sp.misses.data() + at);
     }
   }
   std::memcpy(Rl.centre, p, sizeof(Rl.centre));
@@ -1557,6 +1590,8 @@ void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feat
   dense_settle(c);
   DM.last = fmx_dense_counts{};
   DM.last_integrated = 0;
+  DM.carve.last = fmx_carve_counts{};
+  DM.carve.last_carved = 0;
   // Rolling (opt-in): the voxels outside the box about the previous scan's pose leave the
   // map before the capacity rule looks at it
   if (DM.on && DM.roll.on && e.init) {
@@ -2745,16 +2780,17 @@ fmx_status fmx_dense_stats(fmx_ctx* c, uint64_t out[4]) {
   });
 }
 
-fmx_status fmx_dense_download(fmx_ctx* c, uint32_t min_hits, double* xyz, uint64_t* scan, uint32_t* index,
-                              uint32_t* hits, uint32_t* n) {
+fmx_status fmx_carve_download(fmx_ctx* c, uint32_t min_hits, uint32_t miss_num, uint32_t miss_den,
+                              const fmx_voxel_arrays* arrays, uint32_t* n) {
   return guard<false>(c, [&] {
     auto& D = c->dense;
     if (!D.on) throw StatusError(FMX_E_STATE, "the dense map is not enabled (fmx_dense_configure)");
     dense_settle(c);
     if (!n) throw StatusError(FMX_E_INVAL, "null count");
+    const fmx_voxel_arrays A = arrays ? *arrays : fmx_voxel_arrays{};
     const uint32_t mh = min_hits ? min_hits : 1;
-    const uint32_t count = run_dense_count(c, mh, c->stream);
-    if (!xyz && !scan && !index && !hits) {  // the sizing call
+    const uint32_t count = run_dense_count(c, mh, miss_num, miss_den, c->stream);
+    if (!A.xyz && !A.scan && !A.index && !A.hits && !A.misses) {  // the sizing call
       *n = count;
       return;
     }
@@ -2762,24 +2798,38 @@ fmx_status fmx_dense_download(fmx_ctx* c, uint32_t min_hits, double* xyz, uint64
       throw StatusError(FMX_E_SIZE, "dense map download: room for " + std::to_string(*n) + " of " +
                                         std::to_string(count) + " voxels");
     if (count) {
-      run_dense_compact(c, mh, count, c->stream);
+      const bool with_misses = A.misses && D.carve.have;
+      if (with_misses) D.carve.o_miss.ensure(count);
+      run_dense_compact(c, mh, miss_num, miss_den, with_misses, count, c->stream);
       std::vector<unsigned long long> tag;
-      if (scan || index) {
+      if (A.scan || A.index) {
         tag.resize(count);
         FMX_HIP(hipMemcpyAsync(tag.data(), D.o_tag.p, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                c->stream));
       }
-      if (xyz)
-        FMX_HIP(hipMemcpyAsync(xyz, D.o_xyz.p, 3 * (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      if (hits) FMX_HIP(hipMemcpyAsync(hits, D.o_hits.p, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+      if (A.xyz)
+        FMX_HIP(hipMemcpyAsync(A.xyz, D.o_xyz.p, 3 * (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      if (A.hits)
+        FMX_HIP(hipMemcpyAsync(A.hits, D.o_hits.p, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+      if (with_misses)
+        FMX_HIP(hipMemcpyAsync(A.misses, D.carve.o_miss.p, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               c->stream));
+      else if (A.misses)
+        std::memset(A.misses, 0, (size_t)count * sizeof(uint32_t));  // carving never enabled: reads 0
       FMX_HIP(hipStreamSynchronize(c->stream));
       for (size_t i = 0; i < tag.size(); ++i) {  // the host keeps the integration -> scan_idx table
-        if (scan) scan[i] = D.seq_scan.at((size_t)(tag[i] >> 32));
-        if (index) index[i] = (uint32_t)tag[i];
+        if (A.scan) A.scan[i] = D.seq_scan.at((size_t)(tag[i] >> 32));
+        if (A.index) A.index[i] = (uint32_t)tag[i];
       }
     }
     *n = count;
   });
+}
+
+fmx_status fmx_dense_download(fmx_ctx* c, uint32_t min_hits, double* xyz, uint64_t* scan, uint32_t* index,
+                              uint32_t* hits, uint32_t* n) {
+  const fmx_voxel_arrays A{xyz, scan, index, hits, nullptr};
+  return fmx_carve_download(c, min_hits, 0, 0, &A, n);
 }
 
 fmx_status fmx_dense_clear(fmx_ctx* c) {
@@ -2839,11 +2889,12 @@ fmx_status fmx_roll_count(fmx_ctx* c, const double centre[3], const uint32_t hal
   });
 }
 
-fmx_status fmx_roll_evict(fmx_ctx* c, const double centre[3], const uint32_t half[3], double* xyz, uint64_t* scan,
-                          uint32_t* index, uint32_t* hits, uint32_t* n) {
+fmx_status fmx_carve_evict(fmx_ctx* c, const double centre[3], const uint32_t half[3],
+                           const fmx_voxel_arrays* arrays, uint32_t* n) {
   return guard<false>(c, [&] {
     roll_need_map(c);
-    const bool any = xyz || scan || index || hits;
+    const fmx_voxel_arrays A = arrays ? *arrays : fmx_voxel_arrays{};
+    const bool any = A.xyz || A.scan || A.index || A.hits || A.misses;
     if (any && !n) throw StatusError(FMX_E_INVAL, "null count");
     long long cc[3];
     roll_check_box(c, centre, half, cc);
@@ -2856,36 +2907,107 @@ fmx_status fmx_roll_evict(fmx_ctx* c, const double centre[3], const uint32_t hal
                                         " evicted voxels");
     if (evicted) {
       roll_rebuild(c, cc, half, kept, evicted);
-      if (any) roll_fetch(c, evicted, xyz, scan, index, hits);
+      if (any) roll_fetch(c, evicted, A.xyz, A.scan, A.index, A.hits, A.misses);
     }
     if (n) *n = evicted;
   });
 }
 
-fmx_status fmx_roll_drain(fmx_ctx* c, double* xyz, uint64_t* scan, uint32_t* index, uint32_t* hits, uint32_t* n) {
+fmx_status fmx_roll_evict(fmx_ctx* c, const double centre[3], const uint32_t half[3], double* xyz, uint64_t* scan,
+                          uint32_t* index, uint32_t* hits, uint32_t* n) {
+  const fmx_voxel_arrays A{xyz, scan, index, hits, nullptr};
+  return fmx_carve_evict(c, centre, half, &A, n);
+}
+
+fmx_status fmx_carve_drain(fmx_ctx* c, const fmx_voxel_arrays* arrays, uint32_t* n) {
   return guard<false>(c, [&] {
     roll_need_map(c);
     if (!n) throw StatusError(FMX_E_INVAL, "null count");
+    const fmx_voxel_arrays A = arrays ? *arrays : fmx_voxel_arrays{};
     auto& Rl = c->dense.roll;
-    if (Rl.sp_scan.size() > 0xFFFFFFFFull) throw StatusError(FMX_E_SIZE, "the spill holds more than 2^32 - 1 voxels");
-    const uint32_t count = (uint32_t)Rl.sp_scan.size();
-    if (!xyz && !scan && !index && !hits) {  // the sizing call
+    if (Rl.sp.size() > 0xFFFFFFFFull) throw StatusError(FMX_E_SIZE, "the spill holds more than 2^32 - 1 voxels");
+    const uint32_t count = (uint32_t)Rl.sp.size();
+    if (!A.xyz && !A.scan && !A.index && !A.hits && !A.misses) {  // the sizing call
       *n = count;
       return;
     }
     if (*n < count)
       throw StatusError(FMX_E_SIZE, "roll drain: room for " + std::to_string(*n) + " of " + std::to_string(count) + " voxels");
-    if (count) {
-      if (xyz) std::memcpy(xyz, Rl.sp_xyz.data(), 3 * (size_t)count * sizeof(double));
-      if (scan) std::memcpy(scan, Rl.sp_scan.data(), (size_t)count * sizeof(uint64_t));
-      if (index) std::memcpy(index, Rl.sp_index.data(), (size_t)count * sizeof(uint32_t));
-      if (hits) std::memcpy(hits, Rl.sp_hits.data(), (size_t)count * sizeof(uint32_t));
-    }
-    Rl.sp_xyz.clear();
-    Rl.sp_scan.clear();
-    Rl.sp_index.clear();
-    Rl.sp_hits.clear();
+    Rl.sp.drain(A.xyz, A.scan, A.index, A.hits, A.misses);
     *n = count;
+  });
+}
+
+fmx_status fmx_roll_drain(fmx_ctx* c, double* xyz, uint64_t* scan, uint32_t* index, uint32_t* hits, uint32_t* n) {
+  const fmx_voxel_arrays A{xyz, scan, index, hits, nullptr};
+  return fmx_carve_drain(c, &A, n);
+}
+
+// ---- carving the dense map (densemap.hip, the carve block; carve_host.hpp)
+fmx_status fmx_carve_configure(fmx_ctx* c, const fmx_carve_params* p) {
+  return guard<false>(c, [&] {
+    roll_need_map(c);
+    auto& D = c->dense;
+    auto& Cv = D.carve;
+    CarveCfg cfg;
+    const char* why = "";
+    const fmx_status st = carve_check(p, D.max2, &cfg, &why);
+    if (st != FMX_OK) throw StatusError(st, why);
+    dense_settle(c);
+    if (cfg.on && !Cv.have) {
+      // exactly `slots` entries each, as the table's own arrays; nothing kept on a failure
+      DBuf<uint32_t> misses, seen;
+      alloc_exact(misses, D.slots);
+      alloc_exact(seen, D.slots);
+      Cv.cnt.ensure(8);
+      Cv.h_res.ensure(8);
+      std::memset(Cv.h_res.p, 0, 8 * sizeof(unsigned long long));
+      Cv.flag_seq = Cv.pending = 0;
+      FMX_HIP(hipMemsetAsync(misses.p, 0, D.slots * sizeof(uint32_t), c->stream));
+      FMX_HIP(hipMemsetAsync(seen.p, 0, D.slots * sizeof(uint32_t), c->stream));
+      FMX_HIP(hipMemsetAsync(Cv.cnt.p, 0, 8 * sizeof(unsigned long long), c->stream));
+      FMX_HIP(hipStreamSynchronize(c->stream));
+      Cv.misses = std::move(misses);
+      Cv.seen = std::move(seen);
+      Cv.have = true;  // (the per-scan scratch it uses, slot_of, is the integration's own)
+    }
+    Cv.cfg = cfg;
+  });
+}
+
+fmx_status fmx_carve_rays(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double pose34[12],
+                          fmx_carve_counts* counts) {
+  return guard<false>(c, [&] {
+    roll_need_map(c);
+    auto& D = c->dense;
+    auto& Cv = D.carve;
+    if (!Cv.have) throw StatusError(FMX_E_STATE, "carving has not been enabled on this map (fmx_carve_configure)");
+    dense_settle(c);
+    if (!pose34) throw StatusError(FMX_E_INVAL, "null pose");
+    for (int k = 0; k < 12; ++k)
+      if (!std::isfinite(pose34[k])) throw StatusError(FMX_E_INVAL, "non-finite pose");
+    if ((unsigned long long)n >= (1ull << 32)) throw StatusError(FMX_E_INVAL, "a carve holds fewer than 2^32 points");
+    if (n && !xyzw) throw StatusError(FMX_E_INVAL, "null points");
+    fmx_carve_counts out{};
+    if (n && carve_origin_ok(pose34, D.voxel_w)) {
+      const float4* d = reinterpret_cast<const float4*>(xyzw);
+      if (!src_on_dev) {
+        D.in.ensure(n);
+        FMX_HIP(hipMemcpyAsync(D.in.p, xyzw, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        d = D.in.p;
+      }
+      run_carve(c, d, n, pose34, 0, Cv.flag_seq + 1, c->stream);
+      Cv.flag_seq = Cv.pending = Cv.flag_seq + 1;
+      carve_finish(c, &out);  // the caller owns the points again
+    }
+    if (counts) *counts = out;
+  });
+}
+
+fmx_status fmx_carve_last(fmx_ctx* c, fmx_carve_counts* counts, int* carved) {
+  return guard<false>(c, [&] {
+    if (counts) *counts = c->dense.carve.last;
+    if (carved) *carved = c->dense.carve.last_carved;
   });
 }
 
@@ -2895,7 +3017,7 @@ fmx_status fmx_roll_stats(fmx_ctx* c, uint64_t out[6]) {
     const auto& Rl = c->dense.roll;
     out[0] = Rl.rolls;
     out[1] = Rl.evicted_total;
-    out[2] = Rl.sp_scan.size();
+    out[2] = Rl.sp.size();
     out[3] = Rl.last_kept;
     out[4] = Rl.last_evicted;
     out[5] = Rl.last_scan;

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "fmx/fmx.h"
+#include "carve_host.hpp"
 #include "pair_sort_plan.hpp"
 #include "stage.hpp"
 
@@ -224,6 +225,7 @@ enum ProfId {
   PROF_DESKEW,
   PROF_ORGANIZE,
   PROF_DENSE,
+  PROF_CARVE,
   PROF_COUNT
 };
 
@@ -601,16 +603,30 @@ struct fmx_ctx {
       bool have_centre = false;        // register path: the translation the last roll (or the first look) saw
       double centre[3] = {0.0, 0.0, 0.0};
       uint64_t rolls = 0, evicted_total = 0, last_kept = 0, last_evicted = 0, last_scan = 0;
-      // the host spill: resolved scan_idx values, not tags (a later clear cannot invalidate it)
-      std::vector<double> sp_xyz;
-      std::vector<uint64_t> sp_scan;
-      std::vector<uint32_t> sp_index, sp_hits;
+      fmx::Spill sp;                   // the host spill (carve_host.hpp)
       fmx::DBuf<uint32_t> n;           // {inside, outside, evicted cursor, kept cursor}
       // the kept voxels between the split and the reinsert
       fmx::DBuf<unsigned long long> s_key, s_tag;
       fmx::DBuf<uint32_t> s_hits;
       fmx::DBuf<double> s_xyz;
     } roll;
+    // carving (fmx_carve_*; densemap.hip, the carve block): nothing below is allocated, and
+    // nothing launched, unless fmx_carve_configure has enabled it once
+    struct Carve {
+      bool have = false;             // the two arrays exist (enabled at least once on this map)
+      fmx::CarveCfg cfg;             // carve_host.hpp: on, gate, margin, stride, every (resolved)
+      // exactly `slots` entries each (+ 8 B per slot): how often a ray passed through the
+      // voxel; the last integration (its number + 1) that put a point into it
+      fmx::DBuf<uint32_t> misses, seen;
+      fmx::DBuf<unsigned long long> cnt;    // {rays, steps, misses, exempt, ticket << 32 | rays}, 0 between launches
+      fmx::HBuf<unsigned long long> h_res;  // {rays, steps, misses, exempt, -, completion word (low half)}
+      uint32_t flag_seq = 0;         // the completion word's last value
+      uint32_t pending = 0;          // ... of a carve queued and not yet waited for (else 0)
+      fmx::DBuf<uint32_t> o_miss;    // download / eviction: beside o_hits
+      fmx::DBuf<uint32_t> s_miss;    // roll: beside roll.s_hits
+      fmx_carve_counts last{};       // what the last integrating call did (fmx_carve_last)
+      int last_carved = 0;
+    } carve;
   } dense;
 
   // ---- window keypoint store + maps
@@ -969,9 +985,19 @@ void run_dense_integrate(fmx_ctx* c, const float4* d_pts, size_t n, const double
                          uint32_t flag_seq, hipStream_t st);
 // ... the number of voxels with hits >= min_hits (one launch, waits for it); those voxels
 // appended to c->dense.o_xyz / o_tag / o_hits (one launch, queued); the table emptied
-uint32_t run_dense_count(fmx_ctx* c, uint32_t min_hits, hipStream_t st);
-void run_dense_compact(fmx_ctx* c, uint32_t min_hits, uint32_t count, hipStream_t st);
+// (miss_den != 0: only voxels with misses * miss_den <= hits * miss_num; with_misses: the miss
+// counts appended to c->dense.carve.o_miss as well, which the caller has sized)
+uint32_t run_dense_count(fmx_ctx* c, uint32_t min_hits, uint32_t miss_num, uint32_t miss_den, hipStream_t st);
+void run_dense_compact(fmx_ctx* c, uint32_t min_hits, uint32_t miss_num, uint32_t miss_den, bool with_misses,
+                       uint32_t count, hipStream_t st);
 void run_dense_clear(fmx_ctx* c, hipStream_t st);
+// ... carving (c->dense.carve.have): the rays of the n > 0 points at d_pts from pose34's
+// translation through the table.  mark = integration number + 1 after that integration's
+// claim (c->dense.slot_of is its scratch): its voxels are marked first and are exempt;
+// mark = 0: stand-alone, nothing marked, nothing exempt.  The counts and the completion word
+// flag_seq reach c->dense.carve.h_res (the caller has checked the origin's voxel)
+void run_carve(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, uint32_t mark, uint32_t flag_seq,
+               hipStream_t st);
 // ... rolling: {inside, outside} of the box of voxels |v - cc| <= half (one launch, waits for
 // it); then, with c->dense.o_* sized to `evicted` and c->dense.roll.s_* to `kept`, the evicted
 // voxels appended to o_*, the kept ones put back into the emptied table and the device's

@@ -97,6 +97,35 @@ class _RollParams(C.Structure):
     _fields_ = [("enable", C.c_int32), ("half", C.c_uint32 * 3), ("step", C.c_double), ("spill", C.c_int32)]
 
 
+class _CarveParams(C.Structure):
+    _fields_ = [("enable", C.c_int32), ("max_norm_squared", C.c_double), ("margin", C.c_uint32),
+                ("ray_stride", C.c_uint32), ("every", C.c_uint32)]
+
+
+class _CarveCounts(C.Structure):
+    _fields_ = [("rays", C.c_uint32), ("steps", C.c_uint64), ("misses", C.c_uint64), ("exempt", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(rays=int(self.rays), steps=int(self.steps), misses=int(self.misses), exempt=int(self.exempt))
+
+
+class _VoxelArrays(C.Structure):
+    _fields_ = [("xyz", C.c_void_p), ("scan", C.c_void_p), ("index", C.c_void_p), ("hits", C.c_void_p),
+                ("misses", C.c_void_p)]
+
+
+def miss_fraction(max_miss_ratio):
+    """(miss_num, miss_den) of a download's miss filter misses * miss_den <= hits * miss_num:
+    (0, 0), no filter, for None; else the ratio in 1/65536ths, rounded to nearest (0.5 is
+    32768 / 65536), at most 65535."""
+    if max_miss_ratio is None:
+        return 0, 0
+    r = float(max_miss_ratio)
+    if not (r >= 0.0):
+        raise ValueError("max_miss_ratio must be a number >= 0")
+    return int(min(math.floor(r * 65536.0 + 0.5), float((1 << 32) - 1))), 1 << 16
+
+
 class _Counts(C.Structure):
     _fields_ = [("planar", C.c_uint32), ("point", C.c_uint32), ("planar_selected", C.c_uint32)]
 
@@ -131,6 +160,8 @@ EXPORTED = [
     "fmx_dense_configure", "fmx_dense_integrate", "fmx_dense_last", "fmx_dense_stats", "fmx_dense_download",
     "fmx_dense_clear",
     "fmx_roll_configure", "fmx_roll_count", "fmx_roll_evict", "fmx_roll_drain", "fmx_roll_stats",
+    "fmx_carve_configure", "fmx_carve_rays", "fmx_carve_last", "fmx_carve_download", "fmx_carve_evict",
+    "fmx_carve_drain",
 ]
 
 PAIR_SORT_FORMS = ("none", "per-block", "tail-scanned", "scatter-scanned")
@@ -698,21 +729,36 @@ class Context:
         self._chk(self._L.fmx_dense_stats(self.h, _p(s)))
         return dict(voxels=int(s[0]), max_voxels=int(s[1]), integrations=int(s[2]), slots=int(s[3]))
 
-    def dense_download(self, min_hits: int = 1) -> dict:
-        """fmx_dense_download: the voxels with at least min_hits points, in no particular
+    def _voxel_arrays(self, m: int, misses: bool):
+        """Arrays for m voxels, the fmx_voxel_arrays over them and the dict a caller gets."""
+        out = dict(points=np.zeros((m, 3), np.float64), scan=np.zeros(m, np.uint64), index=np.zeros(m, np.uint32),
+                   hits=np.zeros(m, np.uint32))
+        if misses:
+            out["misses"] = np.zeros(m, np.uint32)
+        A = _VoxelArrays()
+        A.xyz, A.scan, A.index, A.hits = (out[k].ctypes.data for k in ("points", "scan", "index", "hits"))
+        A.misses = out["misses"].ctypes.data if misses else None
+        return A, out
+
+    def _with_misses(self, misses, filtered=False) -> bool:
+        return bool(getattr(self, "_carve", False) or filtered) if misses is None else bool(misses)
+
+    def dense_download(self, min_hits: int = 1, max_miss_ratio=None, misses=None) -> dict:
+        """fmx_carve_download: the voxels with at least min_hits points, in no particular
         order: points (N, 3) float64 in the world, scan (N,) uint64 and index (N,) uint32 of
-        each voxel's representative, hits (N,) uint32."""
+        each voxel's representative, hits (N,) uint32.  With max_miss_ratio only the voxels
+        with misses <= max_miss_ratio * hits (the integer rule of miss_fraction).  misses (N,)
+        uint32 is returned as well once carve_configure has been called on this context, with
+        a max_miss_ratio, or with misses=True; a context that never carves reads as before."""
+        num, den = miss_fraction(max_miss_ratio)
+        args = (C.c_uint32(min_hits), C.c_uint32(num), C.c_uint32(den))
         n = C.c_uint32(0)
-        self._chk(self._L.fmx_dense_download(self.h, C.c_uint32(min_hits), None, None, None, None, C.byref(n)))
+        self._chk(self._L.fmx_carve_download(self.h, *args, None, C.byref(n)))
         m = int(n.value)
-        pts = np.zeros((m, 3), np.float64)
-        scan = np.zeros(m, np.uint64)
-        index = np.zeros(m, np.uint32)
-        hits = np.zeros(m, np.uint32)
+        A, out = self._voxel_arrays(m, self._with_misses(misses, max_miss_ratio is not None))
         if m:
-            self._chk(self._L.fmx_dense_download(self.h, C.c_uint32(min_hits), _p(pts), _p(scan), _p(index), _p(hits),
-                                                 C.byref(n)))
-        return dict(points=pts[:n.value], scan=scan[:n.value], index=index[:n.value], hits=hits[:n.value])
+            self._chk(self._L.fmx_carve_download(self.h, *args, C.byref(A), C.byref(n)))
+        return {k: v[:n.value] for k, v in out.items()}
 
     def dense_clear(self):
         self._chk(self._L.fmx_dense_clear(self.h))
@@ -742,34 +788,67 @@ class Context:
         self._chk(self._L.fmx_roll_count(self.h, _p(c), _p(h), _p(out)))
         return int(out[0]), int(out[1])
 
-    def roll_evict(self, centre, half, discard: bool = False) -> dict:
-        """fmx_roll_evict: the voxels outside the box leave the map and are returned like
-        dense_download's (empty arrays with discard=True)."""
+    def roll_evict(self, centre, half, discard: bool = False, misses=None) -> dict:
+        """fmx_carve_evict: the voxels outside the box leave the map and are returned like
+        dense_download's (empty arrays with discard=True; misses as there)."""
         c, h = self._roll_box(centre, half)
         m = 0 if discard else self.roll_count(c, h)[1]
-        pts = np.zeros((m, 3), np.float64)
-        scan = np.zeros(m, np.uint64)
-        index = np.zeros(m, np.uint32)
-        hits = np.zeros(m, np.uint32)
+        A, out = self._voxel_arrays(m, self._with_misses(misses))
         n = C.c_uint32(m)
         if discard:
-            self._chk(self._L.fmx_roll_evict(self.h, _p(c), _p(h), None, None, None, None, C.byref(n)))
+            self._chk(self._L.fmx_carve_evict(self.h, _p(c), _p(h), None, C.byref(n)))
         elif m:
-            self._chk(self._L.fmx_roll_evict(self.h, _p(c), _p(h), _p(pts), _p(scan), _p(index), _p(hits), C.byref(n)))
-        return dict(points=pts[:m], scan=scan[:m], index=index[:m], hits=hits[:m])
+            self._chk(self._L.fmx_carve_evict(self.h, _p(c), _p(h), C.byref(A), C.byref(n)))
+        return {k: v[:m] for k, v in out.items()}
 
-    def roll_drain(self) -> dict:
-        """fmx_roll_drain: the voxels the register path's rolls evicted since the last drain."""
+    def roll_drain(self, misses=None) -> dict:
+        """fmx_carve_drain: the voxels the register path's rolls evicted since the last drain
+        (misses as in dense_download)."""
         n = C.c_uint32(0)
-        self._chk(self._L.fmx_roll_drain(self.h, None, None, None, None, C.byref(n)))
+        self._chk(self._L.fmx_carve_drain(self.h, None, C.byref(n)))
         m = int(n.value)
-        pts = np.zeros((m, 3), np.float64)
-        scan = np.zeros(m, np.uint64)
-        index = np.zeros(m, np.uint32)
-        hits = np.zeros(m, np.uint32)
+        A, out = self._voxel_arrays(m, self._with_misses(misses))
         if m:
-            self._chk(self._L.fmx_roll_drain(self.h, _p(pts), _p(scan), _p(index), _p(hits), C.byref(n)))
-        return dict(points=pts[:n.value], scan=scan[:n.value], index=index[:n.value], hits=hits[:n.value])
+            self._chk(self._L.fmx_carve_drain(self.h, C.byref(A), C.byref(n)))
+        return {k: v[:n.value] for k, v in out.items()}
+
+    # ---------------------------------------------------------------- carving the dense map
+    def carve_configure(self, enable: bool = True, max_norm_squared: float = 0.0, margin: int = 1,
+                        ray_stride: int = 1, every: int = 1):
+        """fmx_carve_configure (any time once the dense map is on): integrations also cast a
+        ray from the sensor to every point they took (within max_norm_squared, 0 = the dense
+        gate's; every ray_stride-th input index; every `every`-th integration) and each stored
+        voxel counts the rays that passed through it, except in the last `margin` voxels
+        before the return."""
+        p = _CarveParams()
+        p.enable = int(bool(enable))
+        p.max_norm_squared = float(max_norm_squared)
+        p.margin = int(margin)
+        p.ray_stride = int(ray_stride)
+        p.every = int(every)
+        self._chk(self._L.fmx_carve_configure(self.h, C.byref(p)))
+        self._carve = True  # profile_read lists the "carve" id, the downloads carry misses, from here on
+
+    def carve_rays(self, points, pose34) -> dict:
+        """fmx_carve_rays: the rays of (N, 4) float32 points at pose34 against the map as it
+        stands; integrates nothing, exempts nothing.  Returns rays, steps, misses, exempt."""
+        on_dev, ptr, n, keep = _scan_ptr(points)
+        pose = np.ascontiguousarray(pose34, np.float64).reshape(12)
+        if on_dev:
+            _ready(keep)
+        cnt = _CarveCounts()
+        self._chk(self._L.fmx_carve_rays(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev), _p(pose),
+                                         C.byref(cnt)))
+        del keep
+        return cnt.as_dict()
+
+    def carve_last(self):
+        """fmx_carve_last: (counts dict, carved) of the last dense_integrate / register_scan /
+        register_cloud."""
+        cnt = _CarveCounts()
+        flag = C.c_int(0)
+        self._chk(self._L.fmx_carve_last(self.h, C.byref(cnt), C.byref(flag)))
+        return cnt.as_dict(), int(flag.value)
 
     def roll_stats(self) -> dict:
         s = np.zeros(6, np.uint64)
@@ -856,11 +935,12 @@ class Context:
 
     def profile_read(self) -> dict:
         """Per kernel id: ms, launches, bytes since the last reset.  The "dense" id is
-        listed once dense_configure has been called: a context that never configures the
-        map reads exactly as before."""
+        listed once dense_configure has been called, the "carve" id once carve_configure has:
+        a context that never configures them reads exactly as before."""
         n = self._L.fmx_profile_count()
-        if not getattr(self, "_dense", False) and self._L.fmx_profile_name(n - 1) == b"dense":
-            n -= 1
+        for name, flag in ((b"carve", "_carve"), (b"dense", "_dense")):  # the last ids, in this order
+            if not getattr(self, flag, False) and self._L.fmx_profile_name(n - 1) == name:
+                n -= 1
         ms = np.zeros(n)
         la = np.zeros(n, np.uint64)
         by = np.zeros(n)
@@ -1055,6 +1135,7 @@ class FORM:
         self._organize = None  # set_organize's arguments, applied by initialize()
         self._dense = None  # set_dense_map's arguments, applied by initialize()
         self._roll = None  # set_dense_roll's arguments, applied by initialize() after the dense map
+        self._carve = None  # set_dense_carve's arguments, applied by initialize() after the dense map
         self._scan_period = None  # seconds, from set_lidar_params when the parameters carry one
 
     @staticmethod
@@ -1137,6 +1218,11 @@ class FORM:
             w = self._dense["voxel_width"]
             half = [int(math.ceil(h / w)) for h in self._roll["half_extent_m"]]
             self._est.roll_configure(self._roll["enable"], half, self._roll["step_m"], self._roll["spill"])
+        if self._carve is not None:
+            if self._dense is None:
+                raise ValueError("set_dense_carve needs set_dense_map")
+            c = self._carve
+            self._est.carve_configure(c["enable"], c["max_range_m"] ** 2, c["margin"], c["ray_stride"], c["every"])
         self._scan = -1
         self._pose = np.eye(4)
 
@@ -1178,6 +1264,17 @@ class FORM:
         h = np.broadcast_to(np.asarray(half_extent_m, np.float64), (3,))
         self._roll = dict(enable=bool(enable), half_extent_m=[float(v) for v in h], step_m=float(step_m),
                           spill=bool(spill))
+
+    def set_dense_carve(self, enable: bool = True, max_range_m: float = 0.0, margin: int = 1, ray_stride: int = 1,
+                        every: int = 1) -> None:
+        """Count, per voxel of the dense map, the rays of later scans that passed through it
+        (fmx_carve_configure), so that dense_map(max_miss_ratio=...) can leave out what moved
+        while the map was built.  max_range_m: only returns nearer than this cast a ray (0: the
+        dense gate's); margin: voxels in front of a return that are left alone; ray_stride,
+        every: cast every n-th point's ray, carve every n-th integration.  Applied by
+        initialize()."""
+        self._carve = dict(enable=bool(enable), max_range_m=float(max_range_m), margin=int(margin),
+                           ray_stride=int(ray_stride), every=int(every))
 
     def add_imu(self, mm) -> None:  # bindings.cpp:144 (unused)
         pass
@@ -1247,14 +1344,19 @@ class FORM:
             out[name] = a
         return out
 
-    def dense_map(self, min_hits: int = 1) -> dict:
+    def dense_map(self, min_hits: int = 1, max_miss_ratio=None) -> dict:
         """The dense voxel map (set_dense_map): one point per voxel with at least min_hits
         points, as dense_download gives it: points (N, 3) in the world (lidar poses, as
-        map()), scan, index and hits; empty before initialize() or with the map off."""
+        map()), scan, index and hits; empty before initialize() or with the map off.  With
+        set_dense_carve also misses, and max_miss_ratio leaves out the voxels that more than
+        that fraction of their hits' worth of rays passed through."""
         if self._est is None or self._dense is None or not self._dense["enable"]:
-            return dict(points=np.zeros((0, 3)), scan=np.zeros(0, np.uint64), index=np.zeros(0, np.uint32),
-                        hits=np.zeros(0, np.uint32))
-        return self._est.dense_download(min_hits)
+            out = dict(points=np.zeros((0, 3)), scan=np.zeros(0, np.uint64), index=np.zeros(0, np.uint32),
+                       hits=np.zeros(0, np.uint32))
+            if self._carve is not None or max_miss_ratio is not None:
+                out["misses"] = np.zeros(0, np.uint32)
+            return out
+        return self._est.dense_download(min_hits, max_miss_ratio)
 
     def dense_evicted(self) -> dict:
         """The voxels the rolling map (set_dense_roll) has evicted since the last call, as

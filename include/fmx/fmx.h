@@ -457,7 +457,8 @@ typedef struct fmx_dense_counts {
   uint32_t invalid;      /* the five sum to n */
 } fmx_dense_counts;
 /* Before the first registration and the first integration of the context (FMX_E_STATE
- * afterwards).  Allocates the table (44 B per slot) and every per-scan buffer: FMX_E_OOM
+ * afterwards).  Allocates the table (44 B per slot; 52 B once carving is enabled, further
+ * down) and every per-scan buffer: FMX_E_OOM
  * when that fails.  FMX_E_INVAL: a voxel width that is not finite and positive, max_voxels
  * 0 or past 2^29, a gate that is NaN, negative or empty (min >= max). */
 fmx_status fmx_dense_configure(fmx_ctx* ctx, const fmx_dense_params* p);
@@ -539,6 +540,92 @@ fmx_status fmx_roll_drain(fmx_ctx* ctx, double* xyz, uint64_t* scan, uint32_t* i
  * evicted by the last roll, index of the scan whose registration ran the last roll}: the
  * register path's rolls only; all 0 when never used. */
 fmx_status fmx_roll_stats(fmx_ctx* ctx, uint64_t out[6]);
+
+/* ---------------- carving the dense voxel map: per-voxel ray miss counts ---------
+ * A voxel of the dense map is never contradicted once it exists, so whatever moved while the
+ * map was built stays in it.  Opt-in: every integrated point also casts a ray from the sensor
+ * to itself, and a stored voxel keeps `misses`, the number of rays that passed through it
+ * (DESIGN.md §Dense map, Carving).  Nothing is ever removed from the table: a download
+ * filters by misses against hits on the way out.  All of it is exact, fp64 without
+ * contraction, one rounding per written operation (tests/carve_ref.py restates it):
+ *   ray      a point i of an integration that is valid, inside the dense gate and in range
+ *            (it counts as added or merged), with r2 < max_norm_squared (the same fp32 r2,
+ *            widened) and i % ray_stride == 0 on the input index;
+ *   ends     e = the point's world point (the integration's expression), o = the pose's
+ *            translation; w the voxel width; a_k = floor(o_k / w), b_k = floor(e_k / w), so b
+ *            is the point's own voxel.  Unless every |a_k| < 2^20 - 1 the call casts no ray;
+ *   walk     cur = a, then exactly S = sum_k |b_k - a_k| steps: v_0 = a ... v_S = b.  With
+ *            d_k = e_k - o_k and s_k = +1 if b_k > a_k else -1: an axis with cur_k != b_k has
+ *            tau_k = ((double)(cur_k + (s_k > 0 ? 1 : 0)) * w - o_k) / d_k, an axis with
+ *            cur_k == b_k has tau_k = +inf; the walk steps cur_k += s_k on the axis with the
+ *            smallest tau_k, the lowest k among equal ones;
+ *   examined the voxels v_s with 0 <= s <= S - 1 - margin.  Each is looked up in the table
+ *            (find only: home slot mix64 of the key & (slots - 1), linear probing up to the key
+ *            or an empty slot).  Absent: nothing.  Present, and a point of this same
+ *            integration fell into it (any valid in-range point, cast or not): exempt, nothing
+ *            (a surface seen at a grazing angle does not carve itself).  Otherwise its misses
+ *            grow by one.
+ * The result is a sum over a set of (ray, voxel) pairs that the definition fixes: it does
+ * not depend on the order the device's threads run in.  A roll keeps a kept voxel's misses
+ * and hands an evicted voxel's over; fmx_dense_clear zeroes them.  Never configured: every
+ * other entry point behaves, allocates and launches exactly as without this block, and
+ * misses reads 0 wherever it is returned. */
+typedef struct fmx_carve_params {
+  int32_t enable;            /* 0: integrations stop carving (the counts so far stay) */
+  double max_norm_squared;   /* the carve gate; 0: the dense gate's max_norm_squared */
+  uint32_t margin;           /* voxels in front of the return that are left alone */
+  uint32_t ray_stride;       /* 0 = 1 */
+  uint32_t every;            /* carve the integrations whose number is a multiple of this; 0 = 1 */
+} fmx_carve_params;
+typedef struct fmx_carve_counts {
+  uint32_t rays;
+  uint64_t steps;            /* voxels examined */
+  uint64_t misses;           /* ... present and not exempt */
+  uint64_t exempt;           /* ... present and exempt */
+} fmx_carve_counts;
+/* At any time once the dense map is on (FMX_E_STATE otherwise); replaces the earlier
+ * parameters.  The first enabling call on a map allocates and zeroes the two arrays (8 B per
+ * slot on top of the table's 44): FMX_E_OOM, the map and the earlier parameters as they were,
+ * when that fails.  FMX_E_INVAL: p NULL, a NaN or negative gate.  Reconfiguring the dense map
+ * drops the arrays and turns carving off. */
+fmx_status fmx_carve_configure(fmx_ctx* ctx, const fmx_carve_params* p);
+/* Stand-alone: the rays of n_points < 2^32 points (host or device memory) at pose34 against
+ * the map as it stands, by the configured gate, margin and stride (`enable` and `every` play
+ * no part).  Integrates nothing, and nothing is exempt.  Returns once the counts are in
+ * (counts may be NULL).  FMX_E_STATE unless carving has been enabled on this map; FMX_E_INVAL
+ * for a non-finite pose or NULL points with n_points > 0. */
+fmx_status fmx_carve_rays(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                          const double pose34[12], fmx_carve_counts* counts);
+/* With carving enabled, fmx_dense_integrate and the register path's integrations whose
+ * integration number (0, 1, 2, ... since the last clear) is a multiple of `every` carve after
+ * integrating: the scan the integration saw, at the same pose.  The call returns once the
+ * rays have read the scan.  A registration never fails because of carving.  What the last
+ * such call (integrate, register_scan, register_cloud) did: its counts and *carved = 1 if it
+ * carved, else 0 with counts all 0.  Either pointer may be NULL. */
+fmx_status fmx_carve_last(fmx_ctx* ctx, fmx_carve_counts* counts, int* carved);
+/* The downloads with misses.  Any array may be NULL and is then skipped. */
+typedef struct fmx_voxel_arrays {
+  double* xyz;
+  uint64_t* scan;
+  uint32_t* index;
+  uint32_t* hits;
+  uint32_t* misses;
+} fmx_voxel_arrays;
+/* fmx_dense_download that takes a voxel iff hits >= max(min_hits, 1) and, when miss_den != 0,
+ * misses * miss_den <= hits * miss_num in 64-bit integers.  The two-call protocol: arrays
+ * NULL, or all five of its pointers NULL, is the sizing call; otherwise *n is the capacity on
+ * entry (FMX_E_SIZE if too small: nothing written) and the count on return.  misses reads 0
+ * on a map that never enabled carving.  FMX_E_STATE unless the dense map is configured and
+ * enabled; FMX_E_INVAL for n NULL.  fmx_dense_download is this call with misses = NULL and
+ * miss_den = 0. */
+fmx_status fmx_carve_download(fmx_ctx* ctx, uint32_t min_hits, uint32_t miss_num, uint32_t miss_den,
+                              const fmx_voxel_arrays* arrays, uint32_t* n);
+/* fmx_roll_evict and fmx_roll_drain with the struct (arrays NULL, or all five pointers NULL:
+ * discard / the sizing call), with their status codes; those two are these with misses =
+ * NULL.  The spill keeps misses. */
+fmx_status fmx_carve_evict(fmx_ctx* ctx, const double centre[3], const uint32_t half[3],
+                           const fmx_voxel_arrays* arrays, uint32_t* n);
+fmx_status fmx_carve_drain(fmx_ctx* ctx, const fmx_voxel_arrays* arrays, uint32_t* n);
 
 /* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
  * pose at the middle of the last registered sweep. */
