@@ -2,9 +2,10 @@
 // include/fmx/fmx.h, fmx_dense_integrate).  A fixed-capacity open-addressed hash of world
 // voxels, structure-of-arrays, 44 B per slot: keys (u64), tags (u64), hits (u32), xyz
 // (3 doubles); 52 B once carving has been enabled (misses and seen, u32 each: the carve
-// block further down).  An integration is two launches on one stream, no host round trip between
-// them; the kernel boundary is the only ordering (no in-kernel device-scope fence: see
-// organize.hip's header for what one per wave costs on gfx950).
+// block further down; the probe block behind it only reads the table).  An integration is
+// two launches on one stream, no host round trip between them; the kernel boundary is the
+// only ordering (no in-kernel device-scope fence: see organize.hip's header for what one per
+// wave costs on gfx950).
 //
 //   claim   one lane per point: classify it (invalid / gated / out of range), compute its
 //           voxel key, find or insert the key's slot (home = mix64(key) & (slots - 1),
@@ -580,6 +581,228 @@ __global__ __launch_bounds__(kDenseThreads) void k_carve_rays(const float4* __re
   }
 }
 
+// ---- probing (DESIGN.md §Dense map, Probing; include/fmx/fmx.h, fmx_probe_points).  The read
+// path: neither launch writes to the table's arrays, so both commute with each other and
+// repeat bit for bit.  One launch per call, on the context stream behind whatever
+// integration or roll is queued there.
+//
+//   points  one lane per point: classify it (the integration's rule without the gate), one
+//           find-only probe of the table; hits, misses, tag and point are loaded only on a
+//           key match.
+//   rays    one lane per ray: the carve's walk from the sensor's voxel to the point's voxel,
+//           which is examined too, its state in registers as in k_carve_rays (no dynamically
+//           indexed array, no LDS, no scratch).  The lane stops at the first voxel that is
+//           present and solid under the filter; each step remembers the tau it was taken at,
+//           so the hit carries the parameter at which the ray entered its voxel.
+//
+// Look-ahead, as the carve's: the path does not depend on what the table holds, so the lane
+// walks FMX_PROBE_AHEAD voxels, issues their home-slot key loads back to back and then
+// examines them in order.  A voxel behind the hit has been loaded and is never looked at:
+// the outputs and `steps` are the definition's, whatever was loaded ahead
+// (FMX_PROBE_AHEAD=1 builds the plain form; tools/probe_cost.py compares the two).
+//
+// Outputs are structure-of-arrays, each entry written by the lane that owns the index, zeros
+// where no voxel is reported; the only shared words are the counters, one atomic per wave
+// and counter (ballot + popcount, the steps a wave sum).
+#ifndef FMX_PROBE_AHEAD
+#define FMX_PROBE_AHEAD 4
+#endif
+
+__device__ __forceinline__ unsigned long long dense_key(int cx, int cy, int cz) {
+  return ((unsigned long long)((long long)cx + kDenseBias) << 42) | ((unsigned long long)((long long)cy + kDenseBias) << 21) |
+         (unsigned long long)((long long)cz + kDenseBias);
+}
+
+// dense_classify without the gate: 0 in range (wp the world point, v its voxel), 1 invalid, 3
+// out of range
+__device__ __forceinline__ int probe_classify(const float4 p, const DenseArgs& a, double wp[3], int v[3]) {
+  if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) || (p.x == 0.0f && p.y == 0.0f && p.z == 0.0f)) return 1;
+  d_xform(a.T.m, (double)p.x, (double)p.y, (double)p.z, wp);
+  const double cx = floor(wp[0] / a.w), cy = floor(wp[1] / a.w), cz = floor(wp[2] / a.w);
+  // in fp64, before the cast (a NaN or an infinity fails the comparison)
+  if (!(fabs(cx) < kDenseLimit && fabs(cy) < kDenseLimit && fabs(cz) < kDenseLimit)) return 3;
+  v[0] = (int)cx, v[1] = (int)cy, v[2] = (int)cz;
+  return 0;
+}
+
+// Find only, from the home slot h whose key word k is already here (bounded by the table: the
+// load is at most 1/2, a chain meets an empty slot): the key's slot, or the dropped marker.
+__device__ __forceinline__ uint32_t probe_find(unsigned long long key, uint32_t h, unsigned long long k,
+                                               const unsigned long long* __restrict__ keys, uint32_t slot_mask) {
+  for (uint32_t probe = 0; probe <= slot_mask; ++probe) {
+    if (k == key) return h;
+    if (k == kDenseEmpty) return kDenseDropped;
+    h = (h + 1) & slot_mask;
+    k = keys[h];
+  }
+  return kDenseDropped;
+}
+
+// Point i's voxel fields: those of `slot` (h its hit count, already here), zeros for the
+// dropped marker.
+__device__ __forceinline__ void probe_store(const ProbeOut& o, uint32_t i, uint32_t slot, uint32_t h, const DenseTake& tk,
+                                            const unsigned long long* __restrict__ tags,
+                                            const double* __restrict__ xyz) {
+  const bool have = slot != kDenseDropped;
+  if (o.tag) o.tag[i] = have ? tags[slot] : 0ull;
+  if (o.hits) o.hits[i] = h;
+  if (o.misses) o.misses[i] = have ? dense_misses(tk, slot) : 0u;
+  if (o.xyz) {
+    double* q = o.xyz + 3 * (size_t)i;
+    q[0] = have ? xyz[3 * (size_t)slot + 0] : 0.0;
+    q[1] = have ? xyz[3 * (size_t)slot + 1] : 0.0;
+    q[2] = have ? xyz[3 * (size_t)slot + 2] : 0.0;
+  }
+}
+
+// cnt: {absent, filtered, solid, out_of_range, invalid}
+__global__ __launch_bounds__(kDenseThreads) void k_probe_points(const float4* __restrict__ pts, uint32_t n, DenseArgs a,
+                                                                DenseTake tk,
+                                                                const unsigned long long* __restrict__ keys,
+                                                                const unsigned long long* __restrict__ tags,
+                                                                const uint32_t* __restrict__ hits,
+                                                                const double* __restrict__ xyz, ProbeOut o,
+                                                                unsigned long long* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * (uint32_t)kDenseThreads + threadIdx.x;
+  int st = -1;  // past the end
+  if (i < n) {
+    double wp[3];
+    int v[3];
+    const int cls = probe_classify(pts[i], a, wp, v);
+    uint32_t slot = kDenseDropped, h = 0;
+    if (cls == 0) {
+      const unsigned long long key = dense_key(v[0], v[1], v[2]);
+      const uint32_t h0 = (uint32_t)mix64(key) & a.slot_mask;
+      slot = probe_find(key, h0, keys[h0], keys, a.slot_mask);
+      st = FMX_PROBE_ABSENT;
+      if (slot != kDenseDropped) {
+        h = hits[slot];
+        st = dense_take(tk, h, slot) ? FMX_PROBE_SOLID : FMX_PROBE_FILTERED;
+      }
+    } else {
+      st = cls == 1 ? FMX_PROBE_INVALID : FMX_PROBE_OUT_OF_RANGE;
+    }
+    o.state[i] = (uint8_t)st;
+    probe_store(o, i, slot, h, tk, tags, xyz);
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const unsigned long long b = __ballot(st == k);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&cnt[k], (unsigned long long)__popcll(b));  // results unused: return-less
+  }
+}
+
+// One step of the carve's walk: the axis with the smallest tau, the lowest among equal ones;
+// only its tau changes.  tin: the tau the step was taken at, where the ray enters the new voxel.
+__device__ __forceinline__ void probe_step(int& c0, int& c1, int& c2, double& t0, double& t1, double& t2, double& tin,
+                                           int b0, int b1, int b2, int s0, int s1, int s2, double o0, double o1,
+                                           double o2, double d0, double d1, double d2, double w, double inf) {
+  if (t0 <= t1 && t0 <= t2) {
+    tin = t0;
+    c0 += s0;
+    t0 = c0 != b0 ? ((double)(c0 + (s0 > 0 ? 1 : 0)) * w - o0) / d0 : inf;
+  } else if (t1 <= t2) {
+    tin = t1;
+    c1 += s1;
+    t1 = c1 != b1 ? ((double)(c1 + (s1 > 0 ? 1 : 0)) * w - o1) / d1 : inf;
+  } else {
+    tin = t2;
+    c2 += s2;
+    t2 = c2 != b2 ? ((double)(c2 + (s2 > 0 ? 1 : 0)) * w - o2) / d2 : inf;
+  }
+}
+
+// cnt: {hit, clear, out_of_range, invalid, steps}
+__global__ __launch_bounds__(kDenseThreads) void k_probe_rays(const float4* __restrict__ pts, uint32_t n, DenseArgs a,
+                                                              DenseTake tk, uint32_t skip,
+                                                              const unsigned long long* __restrict__ keys,
+                                                              const unsigned long long* __restrict__ tags,
+                                                              const uint32_t* __restrict__ hits,
+                                                              const double* __restrict__ xyz, ProbeOut o,
+                                                              unsigned long long* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * (uint32_t)kDenseThreads + threadIdx.x;
+  const double inf = __longlong_as_double(0x7FF0000000000000ll);
+  int cls = -1;      // past the end
+  uint32_t nex = 0;  // voxels to examine: v_skip ... v_S
+  int c0 = 0, c1 = 0, c2 = 0, b0 = 0, b1 = 0, b2 = 0, s0 = 0, s1 = 0, s2 = 0;
+  double o0 = 0.0, o1 = 0.0, o2 = 0.0, d0 = 0.0, d1 = 0.0, d2 = 0.0, t0 = inf, t1 = inf, t2 = inf, tin = 0.0;
+  if (i < n) {
+    double e[3];
+    int b[3];
+    cls = probe_classify(pts[i], a, e, b);
+    if (cls == 0) {
+      o0 = a.T.m[3], o1 = a.T.m[7], o2 = a.T.m[11];
+      // (both in range: the host checked a, the classification b; |c| < 2^20 fits an int)
+      c0 = (int)floor(o0 / a.w), c1 = (int)floor(o1 / a.w), c2 = (int)floor(o2 / a.w);
+      b0 = b[0], b1 = b[1], b2 = b[2];
+      d0 = e[0] - o0, d1 = e[1] - o1, d2 = e[2] - o2;
+      s0 = b0 > c0 ? 1 : -1, s1 = b1 > c1 ? 1 : -1, s2 = b2 > c2 ? 1 : -1;
+      const uint32_t S = (uint32_t)abs(b0 - c0) + (uint32_t)abs(b1 - c1) + (uint32_t)abs(b2 - c2);
+      if (c0 != b0) t0 = ((double)(c0 + (s0 > 0 ? 1 : 0)) * a.w - o0) / d0;
+      if (c1 != b1) t1 = ((double)(c1 + (s1 > 0 ? 1 : 0)) * a.w - o1) / d1;
+      if (c2 != b2) t2 = ((double)(c2 + (s2 > 0 ? 1 : 0)) * a.w - o2) / d2;
+      if (skip <= S) {
+        nex = S - skip + 1u;
+        for (uint32_t s = 0; s < skip; ++s)  // the skipped voxels: walked, not looked up
+          probe_step(c0, c1, c2, t0, t1, t2, tin, b0, b1, b2, s0, s1, s2, o0, o1, o2, d0, d1, d2, a.w, inf);
+      }
+    }
+  }
+  bool hit = false;
+  uint32_t h_at = 0, h_slot = kDenseDropped, h_hits = 0;  // the hit: its place among the examined, its slot and hit count
+  double h_t = inf;
+  for (uint32_t s = 0; s < nex && !hit; s += (uint32_t)FMX_PROBE_AHEAD) {
+    unsigned long long key[FMX_PROBE_AHEAD], k0[FMX_PROBE_AHEAD];
+    uint32_t h0[FMX_PROBE_AHEAD];
+    double te[FMX_PROBE_AHEAD];
+#pragma unroll
+    for (int u = 0; u < FMX_PROBE_AHEAD; ++u) {
+      // (cur stays in the box between a and b while s + u < nex, so each coordinate + bias is a
+      // 21-bit field; past the end voxel the key is not used and the masked slot is not loaded)
+      key[u] = dense_key(c0, c1, c2);
+      h0[u] = (uint32_t)mix64(key[u]) & a.slot_mask;
+      k0[u] = s + (uint32_t)u < nex ? keys[h0[u]] : kDenseEmpty;
+      te[u] = tin;
+      probe_step(c0, c1, c2, t0, t1, t2, tin, b0, b1, b2, s0, s1, s2, o0, o1, o2, d0, d1, d2, a.w, inf);
+    }
+#pragma unroll
+    for (int u = 0; u < FMX_PROBE_AHEAD; ++u) {
+      if (!hit && s + (uint32_t)u < nex) {
+        const uint32_t slot = probe_find(key[u], h0[u], k0[u], keys, a.slot_mask);
+        if (slot != kDenseDropped) {
+          const uint32_t h = hits[slot];
+          if (dense_take(tk, h, slot)) {  // (present and not solid: transparent)
+            hit = true;
+            h_at = s + (uint32_t)u;
+            h_slot = slot;
+            h_hits = h;
+            h_t = te[u];
+          }
+        }
+      }
+    }
+  }
+  int st = -1;
+  if (i < n) {
+    st = cls == 1 ? FMX_PROBE_INVALID : cls == 3 ? FMX_PROBE_OUT_OF_RANGE : hit ? FMX_PROBE_SOLID : FMX_PROBE_ABSENT;
+    o.state[i] = (uint8_t)st;
+    if (o.step) o.step[i] = hit ? skip + h_at : FMX_PROBE_NO_STEP;
+    if (o.t) o.t[i] = h_t;
+    probe_store(o, i, h_slot, h_hits, tk, tags, xyz);
+  }
+  // (per wave: at most 64 * (3 * 2^21 + 1) examined voxels, so the 32-bit sum cannot wrap)
+  const uint32_t w_steps = wave_sum(hit ? h_at + 1u : nex);
+  const unsigned long long bh = __ballot(st == FMX_PROBE_SOLID), bc = __ballot(st == FMX_PROBE_ABSENT),
+                           bo = __ballot(st == FMX_PROBE_OUT_OF_RANGE), bi = __ballot(st == FMX_PROBE_INVALID);
+  if ((threadIdx.x & 63) == 0) {  // results unused: return-less
+    if (bh) atomicAdd(&cnt[0], (unsigned long long)__popcll(bh));
+    if (bc) atomicAdd(&cnt[1], (unsigned long long)__popcll(bc));
+    if (bo) atomicAdd(&cnt[2], (unsigned long long)__popcll(bo));
+    if (bi) atomicAdd(&cnt[3], (unsigned long long)__popcll(bi));
+    if (w_steps) atomicAdd(&cnt[4], (unsigned long long)w_steps);
+  }
+}
+
 static DenseArgs dense_args(const fmx_ctx* c, const double* pose34) {
   const auto& D = c->dense;
   DenseArgs a{};
@@ -646,6 +869,49 @@ void run_carve(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, 
                        Cv.seen.p, Cv.misses.p, Cv.cnt.p, Cv.h_res.d, reinterpret_cast<uint32_t*>(Cv.h_res.d + 5), flag_seq);
     FMX_HIP(hipGetLastError());
   }
+}
+
+// A probe's filter; the miss array wherever it exists (read on a key match only: for the
+// ratio, and for the misses a point reports).
+static DenseTake probe_take_args(const fmx_ctx* c, const ProbeFilter& f) {
+  const auto& Cv = c->dense.carve;
+  return DenseTake{f.min_hits, f.num, f.den, Cv.have ? Cv.misses.p : nullptr};
+}
+
+// what a launch writes per point: the state byte and the arrays asked for
+static double probe_out_bytes(const ProbeOut& o) {
+  return 1.0 + (o.step ? 4.0 : 0.0) + (o.t ? 8.0 : 0.0) + (o.tag ? 8.0 : 0.0) + (o.hits ? 4.0 : 0.0) +
+         (o.misses ? 4.0 : 0.0) + (o.xyz ? 24.0 : 0.0);
+}
+
+void run_probe_points(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, const ProbeFilter& f,
+                      const ProbeOut& o, hipStream_t st) {
+  auto& D = c->dense;
+  const DenseArgs a = dense_args(c, pose34);
+  const uint32_t blocks = (uint32_t)((n + kDenseThreads - 1) / kDenseThreads);
+  FMX_HIP(hipMemsetAsync(D.probe.cnt.p, 0, 8 * sizeof(unsigned long long), st));
+  // DESIGN.md §Dense map, Probing: the point (16), the home slot's key word (8) and what is
+  // written per point; probes past the home slot, and a present voxel's hits, misses, tag and
+  // point (4 + 4 + 8 + 24 at the most), are not known at launch and not counted
+  ProfScope ps(c->prof, PROF_DENSE, (double)n * (24.0 + probe_out_bytes(o)), st);
+  hipLaunchKernelGGL(k_probe_points, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)n, a,
+                     probe_take_args(c, f), D.keys.p, D.tags.p, D.hits.p, D.xyz.p, o, D.probe.cnt.p);
+  FMX_HIP(hipGetLastError());
+}
+
+void run_probe_rays(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, const ProbeFilter& f,
+                    uint32_t skip, const ProbeOut& o, hipStream_t st) {
+  auto& D = c->dense;
+  const DenseArgs a = dense_args(c, pose34);
+  const uint32_t blocks = (uint32_t)((n + kDenseThreads - 1) / kDenseThreads);
+  FMX_HIP(hipMemsetAsync(D.probe.cnt.p, 0, 8 * sizeof(unsigned long long), st));
+  // the point (16) and what is written per ray; the walk's 8 B per examined voxel, + 4 (+ 4
+  // under a miss filter) where one is present, are not known at launch and not counted
+  // (DESIGN.md has the model, the call's own counts give the steps)
+  ProfScope ps(c->prof, PROF_DENSE, (double)n * (16.0 + probe_out_bytes(o)), st);
+  hipLaunchKernelGGL(k_probe_rays, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)n, a,
+                     probe_take_args(c, f), skip, D.keys.p, D.tags.p, D.hits.p, D.xyz.p, o, D.probe.cnt.p);
+  FMX_HIP(hipGetLastError());
 }
 
 // The miss filter of a download; the miss array only where it exists and the filter reads it.

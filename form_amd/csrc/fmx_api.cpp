@@ -1459,14 +1459,15 @@ bool roll_centre_voxel(const fmx_ctx* c, const double centre[3], long long cc[3]
   }
   return true;
 }
-// DBuf::ensure with a failed allocation reported as a capacity error, not a HIP one.
+// DBuf::ensure with a failed allocation reported as a capacity error, not a HIP one (what:
+// whose buffer it is, for the message).
 template <class T>
-void roll_ensure(DBuf<T>& b, size_t n) {
+void roll_ensure(DBuf<T>& b, size_t n, const char* what = "dense map roll") {
   try {
     b.ensure(n);
   } catch (const HipError&) {
     (void)hipGetLastError();
-    throw StatusError(FMX_E_OOM, "dense map roll: device allocation of " + std::to_string(n * sizeof(T)) + " bytes failed");
+    throw StatusError(FMX_E_OOM, std::string(what) + ": device allocation of " + std::to_string(n * sizeof(T)) + " bytes failed");
   }
 }
 // After run_roll_count gave {kept, evicted} with evicted > 0: size the buffers (FMX_E_OOM
@@ -1555,6 +1556,77 @@ void roll_on_register(fmx_ctx* c, uint64_t j, const double p[3], bool due, size_
   Rl.last_kept = kept;
   Rl.last_evicted = evicted;
   Rl.last_scan = j;
+}
+
+// ---- probing (fmx_probe_*; densemap.hip)
+// Both entry points: the checks, the per-call buffers, one launch, the copies out.  rays: the
+// cast (step / t may be asked for, the origin's voxel is checked); otherwise the lookup.
+// cnt: the launch's five counters.
+void probe_call(fmx_ctx* c, bool rays, const float* xyzw, size_t n, int src_on_dev, const double* pose34,
+                uint32_t min_hits, uint32_t miss_num, uint32_t miss_den, uint32_t skip, uint8_t* state, uint32_t* step,
+                double* t, const fmx_voxel_arrays* voxels, unsigned long long cnt[5]) {
+  auto& D = c->dense;
+  auto& P = D.probe;
+  if (!D.on) throw StatusError(FMX_E_STATE, "the dense map is not enabled (fmx_dense_configure)");
+  const char* why = "";
+  const fmx_status chk = probe_check(xyzw, (unsigned long long)n, pose34, &why);
+  if (chk != FMX_OK) throw StatusError(chk, why);
+  if (rays && !probe_origin_ok(pose34, D.voxel_w))
+    throw StatusError(FMX_E_RANGE, "probe: the voxel of the ray origin is out of range");
+  dense_settle(c);
+  for (int k = 0; k < 5; ++k) cnt[k] = 0;
+  if (!n) return;
+  const fmx_voxel_arrays A = voxels ? *voxels : fmx_voxel_arrays{};
+  const bool want_tag = A.scan || A.index;
+  // every buffer before anything is launched or written (FMX_E_OOM when one cannot be had)
+  const auto probe_ensure = [](auto& b, size_t m) { roll_ensure(b, m, "dense map probe"); };
+  probe_ensure(P.cnt, 8);
+  probe_ensure(P.state, n);
+  if (step) probe_ensure(P.step, n);
+  if (t) probe_ensure(P.t, n);
+  if (want_tag) probe_ensure(P.tag, n);
+  if (A.hits) probe_ensure(P.hits, n);
+  if (A.misses) probe_ensure(P.misses, n);
+  if (A.xyz) probe_ensure(P.xyz, 3 * n);
+  if (!src_on_dev) probe_ensure(D.in, n);
+  std::vector<uint8_t> own_state;
+  std::vector<unsigned long long> tag;
+  if (want_tag) {
+    tag.resize(n);
+    if (!state) own_state.resize(n);
+  }
+  uint8_t* h_state = state ? state : (want_tag ? own_state.data() : nullptr);
+  const float4* d = reinterpret_cast<const float4*>(xyzw);
+  if (!src_on_dev) {
+    FMX_HIP(hipMemcpyAsync(D.in.p, xyzw, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    d = D.in.p;
+  }
+  const ProbeOut o{P.state.p,
+                   step ? P.step.p : nullptr,
+                   t ? P.t.p : nullptr,
+                   want_tag ? P.tag.p : nullptr,
+                   A.hits ? P.hits.p : nullptr,
+                   A.misses ? P.misses.p : nullptr,
+                   A.xyz ? P.xyz.p : nullptr};
+  const ProbeFilter f = probe_filter(min_hits, miss_num, miss_den);
+  if (rays)
+    run_probe_rays(c, d, n, pose34, f, skip, o, c->stream);
+  else
+    run_probe_points(c, d, n, pose34, f, o, c->stream);
+  const auto out = [&](void* dst, const void* src, size_t bytes) {
+    if (dst) FMX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  };
+  out(cnt, P.cnt.p, 5 * sizeof(unsigned long long));
+  out(h_state, P.state.p, n);
+  out(step, P.step.p, n * sizeof(uint32_t));
+  out(t, P.t.p, n * sizeof(double));
+  out(want_tag ? tag.data() : nullptr, P.tag.p, n * sizeof(unsigned long long));
+  out(A.hits, P.hits.p, n * sizeof(uint32_t));
+  out(A.misses, P.misses.p, n * sizeof(uint32_t));
+  out(A.xyz, P.xyz.p, 3 * n * sizeof(double));
+  FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns the points again
+  if (want_tag && !probe_resolve(h_state, tag.data(), n, D.seq_scan, A.scan, A.index))
+    throw StatusError(FMX_E_STATE, "probe: a voxel's tag names an integration the context does not know");
 }
 
 // dsk_cells (fmx_register_cloud with deskewing on): the scan's per-cell sweep fractions
@@ -3008,6 +3080,28 @@ fmx_status fmx_carve_last(fmx_ctx* c, fmx_carve_counts* counts, int* carved) {
   return guard<false>(c, [&] {
     if (counts) *counts = c->dense.carve.last;
     if (carved) *carved = c->dense.carve.last_carved;
+  });
+}
+
+// ---- probing the dense map (densemap.hip, the probe block; probe_host.hpp)
+fmx_status fmx_probe_points(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double pose34[12],
+                            uint32_t min_hits, uint32_t miss_num, uint32_t miss_den, uint8_t* state,
+                            const fmx_voxel_arrays* voxels, fmx_probe_point_counts* counts) {
+  return guard<false>(c, [&] {
+    unsigned long long k[5];
+    probe_call(c, false, xyzw, n, src_on_dev, pose34, min_hits, miss_num, miss_den, 0, state, nullptr, nullptr, voxels, k);
+    if (counts)
+      *counts = fmx_probe_point_counts{(uint32_t)k[0], (uint32_t)k[1], (uint32_t)k[2], (uint32_t)k[3], (uint32_t)k[4]};
+  });
+}
+
+fmx_status fmx_probe_rays(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double pose34[12],
+                          uint32_t min_hits, uint32_t miss_num, uint32_t miss_den, uint32_t skip, uint8_t* state,
+                          uint32_t* step, double* t, const fmx_voxel_arrays* voxels, fmx_probe_ray_counts* counts) {
+  return guard<false>(c, [&] {
+    unsigned long long k[5];
+    probe_call(c, true, xyzw, n, src_on_dev, pose34, min_hits, miss_num, miss_den, skip, state, step, t, voxels, k);
+    if (counts) *counts = fmx_probe_ray_counts{(uint32_t)k[0], (uint32_t)k[1], (uint32_t)k[2], (uint32_t)k[3], k[4]};
   });
 }
 

@@ -20,9 +20,21 @@
 #include "fmx/fmx.h"
 #include "carve_host.hpp"
 #include "pair_sort_plan.hpp"
+#include "probe_host.hpp"
 #include "stage.hpp"
 
 namespace fmx {
+
+// Where a probe launch writes its per-point results (device memory, structure-of-arrays, each
+// entry by the lane that owns the index): state always, every other array only where not null.
+struct ProbeOut {
+  uint8_t* state;
+  uint32_t* step;  // rays only
+  double* t;       // rays only
+  unsigned long long* tag;
+  uint32_t *hits, *misses;
+  double* xyz;
+};
 
 struct HipError : std::runtime_error {
   using std::runtime_error::runtime_error;
@@ -627,6 +639,16 @@ struct fmx_ctx {
       fmx_carve_counts last{};       // what the last integrating call did (fmx_carve_last)
       int last_carved = 0;
     } carve;
+    // probing (fmx_probe_*; densemap.hip, the probe block): per-call outputs, grown at first
+    // use; nothing below is allocated, and nothing launched, unless one of those is called
+    struct Probe {
+      fmx::DBuf<uint8_t> state;
+      fmx::DBuf<uint32_t> step, hits, misses;
+      fmx::DBuf<double> t, xyz;
+      fmx::DBuf<unsigned long long> tag;
+      fmx::DBuf<unsigned long long> cnt;  // points: {absent, filtered, solid, out_of_range, invalid}; rays: {hit,
+                                          // clear, out_of_range, invalid, steps}; zeroed by each call
+    } probe;
   } dense;
 
   // ---- window keypoint store + maps
@@ -998,6 +1020,15 @@ void run_dense_clear(fmx_ctx* c, hipStream_t st);
 // flag_seq reach c->dense.carve.h_res (the caller has checked the origin's voxel)
 void run_carve(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, uint32_t mark, uint32_t flag_seq,
                hipStream_t st);
+// ... probing: one lookup (points), or one first-hit segment cast from pose34's translation
+// examining the voxels from `skip` on (rays; the caller has checked the origin's voxel), per
+// point of the n > 0 at d_pts, under the filter f.  The per-point results go to the device
+// arrays of o (n entries each, xyz 3 n; state always, the others where not null), the counts
+// to c->dense.probe.cnt, which the call zeroes first (one launch each, queued; reads only)
+void run_probe_points(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, const ProbeFilter& f,
+                      const ProbeOut& o, hipStream_t st);
+void run_probe_rays(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, const ProbeFilter& f,
+                    uint32_t skip, const ProbeOut& o, hipStream_t st);
 // ... rolling: {inside, outside} of the box of voxels |v - cc| <= half (one launch, waits for
 // it); then, with c->dense.o_* sized to `evicted` and c->dense.roll.s_* to `kept`, the evicted
 // voxels appended to o_*, the kept ones put back into the emptied table and the device's

@@ -114,6 +114,29 @@ class _VoxelArrays(C.Structure):
                 ("misses", C.c_void_p)]
 
 
+class _ProbePointCounts(C.Structure):
+    _fields_ = [("absent", C.c_uint32), ("filtered", C.c_uint32), ("solid", C.c_uint32), ("out_of_range", C.c_uint32),
+                ("invalid", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(absent=int(self.absent), filtered=int(self.filtered), solid=int(self.solid),
+                    out_of_range=int(self.out_of_range), invalid=int(self.invalid))
+
+
+class _ProbeRayCounts(C.Structure):
+    _fields_ = [("hit", C.c_uint32), ("clear", C.c_uint32), ("out_of_range", C.c_uint32), ("invalid", C.c_uint32),
+                ("steps", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(hit=int(self.hit), clear=int(self.clear), out_of_range=int(self.out_of_range),
+                    invalid=int(self.invalid), steps=int(self.steps))
+
+
+# fmx_probe_points / fmx_probe_rays: the per-point state
+PROBE_ABSENT, PROBE_FILTERED, PROBE_SOLID, PROBE_OUT_OF_RANGE, PROBE_INVALID = range(5)
+PROBE_NO_STEP = 0xFFFFFFFF
+
+
 def miss_fraction(max_miss_ratio):
     """(miss_num, miss_den) of a download's miss filter misses * miss_den <= hits * miss_num:
     (0, 0), no filter, for None; else the ratio in 1/65536ths, rounded to nearest (0.5 is
@@ -162,6 +185,7 @@ EXPORTED = [
     "fmx_roll_configure", "fmx_roll_count", "fmx_roll_evict", "fmx_roll_drain", "fmx_roll_stats",
     "fmx_carve_configure", "fmx_carve_rays", "fmx_carve_last", "fmx_carve_download", "fmx_carve_evict",
     "fmx_carve_drain",
+    "fmx_probe_points", "fmx_probe_rays",
 ]
 
 PAIR_SORT_FORMS = ("none", "per-block", "tail-scanned", "scatter-scanned")
@@ -850,6 +874,51 @@ class Context:
         self._chk(self._L.fmx_carve_last(self.h, C.byref(cnt), C.byref(flag)))
         return cnt.as_dict(), int(flag.value)
 
+    # ---------------------------------------------------------------- probing the dense map
+    def probe_points(self, points, pose34, min_hits: int = 1, max_miss_ratio=None) -> dict:
+        """fmx_probe_points: one lookup per (N, 4) float32 point (numpy, or a torch tensor on
+        the host or the device) at pose34, on the device; changes nothing.  Returns state (N,)
+        uint8 (PROBE_ABSENT, _FILTERED: present but not solid under min_hits and
+        max_miss_ratio (miss_fraction's integer rule), _SOLID, _OUT_OF_RANGE, _INVALID), the
+        voxel's points, scan, index, hits and misses where the state is FILTERED or SOLID
+        (zeros elsewhere), and counts (absent, filtered, solid, out_of_range, invalid)."""
+        num, den = miss_fraction(max_miss_ratio)
+        on_dev, ptr, n, keep = _scan_ptr(points)
+        pose = np.ascontiguousarray(pose34, np.float64).reshape(12)
+        if on_dev:
+            _ready(keep)
+        A, out = self._voxel_arrays(n, True)
+        state = np.zeros(n, np.uint8)
+        cnt = _ProbePointCounts()
+        self._chk(self._L.fmx_probe_points(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev), _p(pose),
+                                           C.c_uint32(min_hits), C.c_uint32(num), C.c_uint32(den), _p(state),
+                                           C.byref(A), C.byref(cnt)))
+        del keep
+        return dict(out, state=state, counts=cnt.as_dict())
+
+    def probe_rays(self, points, pose34, min_hits: int = 1, max_miss_ratio=None, skip: int = 0) -> dict:
+        """fmx_probe_rays: one segment cast per (N, 4) float32 point, from pose34's translation
+        to the point's world point through the voxels of the map, the first `skip` voxels of
+        the path left out and the end voxel included; changes nothing.  Returns state (N,)
+        uint8 (PROBE_SOLID: the ray ended in a solid voxel; PROBE_ABSENT: clear;
+        _OUT_OF_RANGE, _INVALID), step (N,) uint32 (the hit voxel's place on the path,
+        PROBE_NO_STEP without a hit), t (N,) float64 (where the ray entered it as a fraction
+        of the segment, +inf without a hit), the hit voxel's points, scan, index, hits and
+        misses, and counts (hit, clear, out_of_range, invalid, steps: the voxels examined)."""
+        num, den = miss_fraction(max_miss_ratio)
+        on_dev, ptr, n, keep = _scan_ptr(points)
+        pose = np.ascontiguousarray(pose34, np.float64).reshape(12)
+        if on_dev:
+            _ready(keep)
+        A, out = self._voxel_arrays(n, True)
+        state, step, t = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.float64)
+        cnt = _ProbeRayCounts()
+        self._chk(self._L.fmx_probe_rays(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev), _p(pose),
+                                         C.c_uint32(min_hits), C.c_uint32(num), C.c_uint32(den), C.c_uint32(skip),
+                                         _p(state), _p(step), _p(t), C.byref(A), C.byref(cnt)))
+        del keep
+        return dict(out, state=state, step=step, t=t, counts=cnt.as_dict())
+
     def roll_stats(self) -> dict:
         s = np.zeros(6, np.uint64)
         self._chk(self._L.fmx_roll_stats(self.h, _p(s)))
@@ -1357,6 +1426,29 @@ class FORM:
                 out["misses"] = np.zeros(0, np.uint32)
             return out
         return self._est.dense_download(min_hits, max_miss_ratio)
+
+    def _probe_args(self, points, pose):
+        if self._est is None or self._dense is None or not self._dense["enable"]:
+            raise RuntimeError("the dense map is off (set_dense_map, then initialize())")
+        if isinstance(points, np.ndarray) and points.ndim == 2 and points.shape[1] == 3:
+            p4 = np.zeros((len(points), 4), np.float32)
+            p4[:, :3] = points
+            points = p4
+        T = self._est.current_pose() if pose is None else np.asarray(pose, np.float64).reshape(-1, 4)[:3]
+        return points, T
+
+    def dense_lookup(self, points, pose=None, min_hits: int = 1, max_miss_ratio=None) -> dict:
+        """Look points of the sensor frame up in the dense map (Context.probe_points): (N, 3)
+        or (N, 4) float32 points at the lidar pose `pose` (3 x 4 or 4 x 4; None: the current
+        one, where the last scan was integrated)."""
+        points, T = self._probe_args(points, pose)
+        return self._est.probe_points(points, T, min_hits, max_miss_ratio)
+
+    def dense_cast(self, points, pose=None, min_hits: int = 1, max_miss_ratio=None, skip: int = 0) -> dict:
+        """Cast the segments from the sensor at `pose` to the points through the dense map
+        (Context.probe_rays; arguments as dense_lookup): the first solid voxel on each."""
+        points, T = self._probe_args(points, pose)
+        return self._est.probe_rays(points, T, min_hits, max_miss_ratio, skip)
 
     def dense_evicted(self) -> dict:
         """The voxels the rolling map (set_dense_roll) has evicted since the last call, as

@@ -627,6 +627,72 @@ fmx_status fmx_carve_evict(fmx_ctx* ctx, const double centre[3], const uint32_t 
                            const fmx_voxel_arrays* arrays, uint32_t* n);
 fmx_status fmx_carve_drain(fmx_ctx* ctx, const fmx_voxel_arrays* arrays, uint32_t* n);
 
+/* ---------------- probing the dense voxel map: lookups and first-hit ray casts ----
+ * Questions about a few thousand places, answered on the device without a download
+ * (DESIGN.md §Dense map, Probing).  Both calls only read: the table, the counters,
+ * fmx_dense_stats, fmx_dense_last, fmx_carve_last, the spill and the estimator are as before.
+ * All of it is exact, fp64 without contraction, one rounding per written operation
+ * (tests/probe_ref.py restates it):
+ *   filter   min_hits, miss_num, miss_den.  A stored voxel is solid iff hits >= max(min_hits, 1)
+ *            and, when miss_den != 0, misses * miss_den <= hits * miss_num in 64-bit integers:
+ *            fmx_carve_download's rule.  misses reads 0 on a map that never enabled carving;
+ *   point    input point i (fp32 xyzw, host or device memory, n_points < 2^32) at pose34 is
+ *            invalid when x, y or z is not finite or x = y = z = 0 (the integration's rule;
+ *            the dense gate plays no part).  Otherwise its world point is the integration's
+ *            expression and its voxel c_k = floor(w_k / voxel_width); out_of_range unless
+ *            every |c_k| < 2^20 - 1, tested in fp64 before the cast;
+ *   lookup   find only: home slot mix64 of the key & (slots - 1), linear probing up to the
+ *            key or an empty slot;
+ *   outputs  host arrays aligned with the input, index i to point i.  Any pointer may be NULL
+ *            (voxels NULL: all five of its pointers NULL) and is then neither computed into
+ *            nor copied.  Where no voxel is reported the five voxel fields are written as
+ *            zeros; scan is the scan_idx of the integration that owns the voxel.
+ * Status codes of both: FMX_E_STATE unless the dense map is configured and enabled;
+ * FMX_E_INVAL for a NULL or non-finite pose, NULL points with n_points > 0 or n_points >=
+ * 2^32; FMX_E_OOM, nothing written, when a per-call device buffer cannot be allocated.
+ * n_points == 0 succeeds with zero counts.  The calls run after whatever integration or roll
+ * is queued and return once the outputs are in.  A context that never calls them allocates
+ * and launches nothing for them. */
+#define FMX_PROBE_ABSENT 0        /* the voxel is not in the map; a ray: no solid voxel examined */
+#define FMX_PROBE_FILTERED 1      /* present but not solid */
+#define FMX_PROBE_SOLID 2         /* present and solid; a ray: it ended in this voxel */
+#define FMX_PROBE_OUT_OF_RANGE 3
+#define FMX_PROBE_INVALID 4
+#define FMX_PROBE_NO_STEP 0xFFFFFFFFu
+typedef struct fmx_probe_point_counts {
+  uint32_t absent;
+  uint32_t filtered;
+  uint32_t solid;
+  uint32_t out_of_range;
+  uint32_t invalid;          /* the five sum to n */
+} fmx_probe_point_counts;
+typedef struct fmx_probe_ray_counts {
+  uint32_t hit;
+  uint32_t clear;
+  uint32_t out_of_range;
+  uint32_t invalid;          /* the four sum to n */
+  uint64_t steps;            /* voxels examined, the hit voxel included and nothing behind it */
+} fmx_probe_ray_counts;
+/* One lookup per point: state[i] is one of the five values above, and for FILTERED and SOLID
+ * the voxel's fields are returned. */
+fmx_status fmx_probe_points(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                            const double pose34[12], uint32_t min_hits, uint32_t miss_num, uint32_t miss_den,
+                            uint8_t* state, const fmx_voxel_arrays* voxels, fmx_probe_point_counts* counts);
+/* One segment cast per point, from the pose's translation o to the point's world point e.
+ * Invalid and out_of_range as above, the latter for the end voxel b; a = floor(o / w) by the
+ * carve's rule: FMX_E_RANGE, nothing written, unless every |a_k| < 2^20 - 1.  The walk is the
+ * carve's, word for word (above, "walk"): v_0 = a ... v_S = b.  Examined, in order: v_s for
+ * skip <= s <= S, the end voxel included (skip: the sensor's own voxels).  The first examined
+ * voxel that is present and solid ends the ray (one present but not solid is transparent):
+ * state SOLID, step[i] = s, t[i] = the tau of the step that entered v_s (0.0 for s = 0; the
+ * range is t |e - o|), and the voxel's fields.  Otherwise state ABSENT, and for every state
+ * but SOLID step[i] = FMX_PROBE_NO_STEP and t[i] = +inf.  counts->steps is the definition's
+ * number, whatever the kernel loads ahead. */
+fmx_status fmx_probe_rays(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                          const double pose34[12], uint32_t min_hits, uint32_t miss_num, uint32_t miss_den,
+                          uint32_t skip, uint8_t* state, uint32_t* step, double* t,
+                          const fmx_voxel_arrays* voxels, fmx_probe_ray_counts* counts);
+
 /* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
  * pose at the middle of the last registered sweep. */
 fmx_status fmx_current_pose(fmx_ctx* ctx, double pose34[12]);
