@@ -2,7 +2,8 @@
 // include/fmx/fmx.h, fmx_dense_integrate).  A fixed-capacity open-addressed hash of world
 // voxels, structure-of-arrays, 44 B per slot: keys (u64), tags (u64), hits (u32), xyz
 // (3 doubles); 52 B once carving has been enabled (misses and seen, u32 each: the carve
-// block further down; the probe block behind it only reads the table).  An integration is
+// block further down; the probe block behind it only reads the table; the upload block behind
+// that puts downloaded voxels back).  An integration is
 // two launches on one stream, no host round trip between them; the kernel boundary is the
 // only ordering (no in-kernel device-scope fence: see organize.hip's header for what one per
 // wave costs on gfx950).
@@ -803,6 +804,129 @@ __global__ __launch_bounds__(kDenseThreads) void k_probe_rays(const float4* __re
   }
 }
 
+// ---- loading voxels back (DESIGN.md §Dense map, Restoring; include/fmx/fmx.h,
+// fmx_upload_voxels).  The inverse of the downloads: entries (world point, owner number, index,
+// hits, misses), staged by the host, go into the table.  Three launches on one stream, the
+// kernel boundary the only ordering, as above.
+//
+//   claim  one lane per entry: classify it (invalid / out of range; no pose, no gate), compute
+//          its key, find or insert the slot word for word as k_dense_claim does, then one
+//          return-less atomicMin on the slot's tag with the temporary tag (temp << 32 | i),
+//          return-less atomicAdds of its hits and, where given and nonzero, its misses, and
+//          the slot (or the dropped marker) into the n-word scratch.  temp is an owner number
+//          larger than every resident one: a resident voxel's tag stays, a new voxel's tag
+//          ends as its lowest input position.  No in-wave merge: uploaded keys are mostly
+//          distinct.
+//   fill   one lane per entry: the lane whose temporary tag equals the slot's is the new
+//          voxel's representative (exactly one: positions are unique), writes the point as
+//          given and marks its own scratch word (bit 31: slots are below 2^30); one atomic
+//          per block counts them.  Nothing writes a tag in this launch.
+//   tag    one lane per entry: a marked lane stores the final tag (owner << 32 | index) with a
+//          plain store.  Nothing reads a tag in this launch, and each tag word has one writer.
+//          Its first lane adds the fill's count to the device's voxel total.
+//
+// The content does not depend on the order the lanes run in: keys are only inserted, the
+// temporary tag is a minimum over a fixed set, hits and misses are sums, and point and final
+// tag of a slot are written by exactly one lane.  seen is not touched: a resident voxel keeps
+// its mark, a new voxel's slot reads 0 (clear and roll leave empty slots at 0).
+constexpr uint32_t kUploadWinner = 0x80000000u;
+
+// 0 valid (key set), 1 invalid, 3 out of range; dead: hits given and 0
+__device__ __forceinline__ int upload_classify(double x, double y, double z, bool dead, double w,
+                                               unsigned long long* key) {
+  if (!(isfinite(x) && isfinite(y) && isfinite(z)) || dead) return 1;
+  const double cx = floor(x / w), cy = floor(y / w), cz = floor(z / w);
+  // in fp64, before the cast (an infinite quotient fails the comparison)
+  if (!(fabs(cx) < kDenseLimit && fabs(cy) < kDenseLimit && fabs(cz) < kDenseLimit)) return 3;
+  *key = ((unsigned long long)((long long)cx + kDenseBias) << 42) |
+         ((unsigned long long)((long long)cy + kDenseBias) << 21) | (unsigned long long)((long long)cz + kDenseBias);
+  return 0;
+}
+
+// in_hits / in_miss: null (1 / 0 per entry); misses: the table's array (there whenever in_miss
+// is); cnt: {invalid, out_of_range, added}
+__global__ __launch_bounds__(kDenseThreads) void k_upload_claim(
+    const double* __restrict__ in_xyz, const uint32_t* __restrict__ in_hits, const uint32_t* __restrict__ in_miss,
+    uint32_t n, double w, uint32_t slot_mask, uint32_t temp, unsigned long long* keys, unsigned long long* tags,
+    uint32_t* hits, uint32_t* misses, uint32_t* __restrict__ slot_of, uint32_t* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * (uint32_t)kDenseThreads + threadIdx.x;
+  int cls = -1;  // past the end
+  unsigned long long key = 0;
+  uint32_t h_in = 1;
+  if (i < n) {
+    if (in_hits) h_in = in_hits[i];
+    const double* p = in_xyz + 3 * (size_t)i;
+    cls = upload_classify(p[0], p[1], p[2], h_in == 0, w, &key);
+  }
+  uint32_t slot = kDenseDropped;
+  if (cls == 0) {
+    uint32_t h = (uint32_t)mix64(key) & slot_mask;
+    // (bounded by the table: the host's capacity rule leaves half the slots empty)
+    for (uint32_t probe = 0; probe <= slot_mask; ++probe) {
+      unsigned long long k = keys[h];  // a stale empty is settled by the CAS; keys never change once set
+      if (k == kDenseEmpty) k = atomicCAS(&keys[h], kDenseEmpty, key);
+      if (k == kDenseEmpty || k == key) {
+        slot = h;
+        break;
+      }
+      h = (h + 1) & slot_mask;
+    }
+    if (slot != kDenseDropped) {
+      atomicMin(&tags[slot], ((unsigned long long)temp << 32) | (unsigned long long)i);  // results unused:
+      atomicAdd(&hits[slot], h_in);                                                       // return-less
+      if (in_miss) {
+        const uint32_t m = in_miss[i];
+        if (m) atomicAdd(&misses[slot], m);
+      }
+    }
+  }
+  if (i < n) slot_of[i] = slot;
+  const unsigned long long bi = __ballot(cls == 1), bo = __ballot(cls == 3);
+  if ((threadIdx.x & 63) == 0) {
+    if (bi) atomicAdd(&cnt[0], (uint32_t)__popcll(bi));
+    if (bo) atomicAdd(&cnt[1], (uint32_t)__popcll(bo));
+  }
+}
+
+__global__ __launch_bounds__(kDenseFillThreads) void k_upload_fill(const double* __restrict__ in_xyz, uint32_t n,
+                                                                   uint32_t temp,
+                                                                   const unsigned long long* __restrict__ tags,
+                                                                   uint32_t* __restrict__ slot_of,
+                                                                   double* __restrict__ xyz, uint32_t* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * (uint32_t)kDenseFillThreads + threadIdx.x;
+  bool winner = false;
+  if (i < n) {
+    const uint32_t slot = slot_of[i];
+    if (slot != kDenseDropped && tags[slot] == (((unsigned long long)temp << 32) | (unsigned long long)i)) {
+      winner = true;
+      const double* p = in_xyz + 3 * (size_t)i;
+      double* o = xyz + 3 * (size_t)slot;
+      o[0] = p[0];
+      o[1] = p[1];
+      o[2] = p[2];
+      slot_of[i] = slot | kUploadWinner;  // (this lane's own word)
+    }
+  }
+  const uint32_t mine = (uint32_t)__syncthreads_count(winner);
+  if (threadIdx.x == 0 && mine) atomicAdd(&cnt[2], mine);  // result unused: return-less
+}
+
+// in_index: null (0 per entry); up_cnt: the upload's counters, complete (the fill's launch
+// has ended); cnt[3]: the device's voxel total (k_dense_fill adds to it)
+__global__ __launch_bounds__(kDenseThreads) void k_upload_tag(const uint32_t* __restrict__ slot_of,
+                                                              const uint32_t* __restrict__ in_owner,
+                                                              const uint32_t* __restrict__ in_index, uint32_t n,
+                                                              unsigned long long* __restrict__ tags,
+                                                              const uint32_t* __restrict__ up_cnt,
+                                                              uint32_t* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * (uint32_t)kDenseThreads + threadIdx.x;
+  if (i == 0) cnt[3] += up_cnt[2];  // (the only lane of the launch that touches the word)
+  if (i >= n) return;
+  const uint32_t s = slot_of[i];
+  if (s == kDenseDropped || !(s & kUploadWinner)) return;
+  tags[s & ~kUploadWinner] = ((unsigned long long)in_owner[i] << 32) | (unsigned long long)(in_index ? in_index[i] : 0u);
+}
+
 static DenseArgs dense_args(const fmx_ctx* c, const double* pose34) {
   const auto& D = c->dense;
   DenseArgs a{};
@@ -912,6 +1036,46 @@ void run_probe_rays(fmx_ctx* c, const float4* d_pts, size_t n, const double* pos
   hipLaunchKernelGGL(k_probe_rays, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)n, a,
                      probe_take_args(c, f), skip, D.keys.p, D.tags.p, D.hits.p, D.xyz.p, o, D.probe.cnt.p);
   FMX_HIP(hipGetLastError());
+}
+
+void run_dense_upload(fmx_ctx* c, uint32_t n, bool have_index, bool have_hits, bool have_misses, uint32_t temp,
+                      hipStream_t st) {
+  auto& D = c->dense;
+  auto& U = D.upload;
+  const uint32_t* in_hits = have_hits ? U.hits.p : nullptr;
+  const uint32_t* in_miss = have_misses ? U.misses.p : nullptr;
+  FMX_HIP(hipMemsetAsync(U.cnt.p, 0, 4 * sizeof(uint32_t), st));
+  {
+    const uint32_t blocks = (n + kDenseThreads - 1) / kDenseThreads;
+    // DESIGN.md §Dense map, Restoring: the entry's point (24) and, where given, its hits and
+    // misses (4 + 4), the key word it finds or claims (8), the tag and hit atomics (8 + 4),
+    // the miss atomic where given (4) and its slot word (4); probes past the home slot not
+    // counted
+    ProfScope ps(c->prof, PROF_DENSE, (double)n * (48.0 + (have_hits ? 4.0 : 0.0) + (have_misses ? 8.0 : 0.0)), st);
+    hipLaunchKernelGGL(k_upload_claim, dim3(blocks), dim3(kDenseThreads), 0, st, U.xyz.p, in_hits, in_miss, n, D.voxel_w,
+                       (uint32_t)(D.slots - 1), temp, D.keys.p, D.tags.p, D.hits.p,
+                       D.carve.have ? D.carve.misses.p : nullptr, U.slot.p, U.cnt.p);
+    FMX_HIP(hipGetLastError());
+  }
+  {
+    const uint32_t blocks = (n + kDenseFillThreads - 1) / kDenseFillThreads;
+    // the slot word (4) and the slot's tag (8) per entry; a representative's point read and
+    // written and its slot word marked (24 + 24 + 4 per new voxel) are not known at launch
+    // and not counted
+    ProfScope ps(c->prof, PROF_DENSE, (double)n * 12.0, st);
+    hipLaunchKernelGGL(k_upload_fill, dim3(blocks), dim3(kDenseFillThreads), 0, st, U.xyz.p, n, temp, D.tags.p, U.slot.p,
+                       D.xyz.p, U.cnt.p);
+    FMX_HIP(hipGetLastError());
+  }
+  {
+    const uint32_t blocks = (n + kDenseThreads - 1) / kDenseThreads;
+    // the slot word (4) per entry; a representative's owner, index and tag (4 + 4 + 8 per new
+    // voxel) are not known at launch and not counted
+    ProfScope ps(c->prof, PROF_DENSE, (double)n * 4.0, st);
+    hipLaunchKernelGGL(k_upload_tag, dim3(blocks), dim3(kDenseThreads), 0, st, U.slot.p, U.owner.p,
+                       have_index ? U.index.p : nullptr, n, D.tags.p, U.cnt.p, D.cnt.p);
+    FMX_HIP(hipGetLastError());
+  }
 }
 
 // The miss filter of a download; the miss array only where it exists and the filter reads it.

@@ -1385,6 +1385,7 @@ void dense_release(fmx_ctx* c) {
   D.carve.last_carved = 0;
   D.max_voxels = D.slots = D.voxels = 0;
   D.seq_scan.clear();
+  D.integrations = 0;
   D.roll.on = D.roll.have_centre = false;  // (a roll configuration belongs to the map it was made for)
 }
 // Queue the integration of the n device points at d (the capacity rule checked by the
@@ -1398,9 +1399,11 @@ uint32_t dense_queue(fmx_ctx* c, const float4* d, size_t n, const double* pose34
   auto& Cv = D.carve;
   D.used = true;
   uint32_t flag = 0;
+  // the tag's owner number; the integration's own number, which `every` counts, is apart
+  // from it once an upload has drawn owner numbers too (fmx_upload_voxels)
   const uint32_t seq = (uint32_t)D.seq_scan.size();
   Cv.last = fmx_carve_counts{};
-  Cv.last_carved = Cv.have && Cv.cfg.on && seq % Cv.cfg.every == 0 ? 1 : 0;
+  Cv.last_carved = Cv.have && Cv.cfg.on && D.integrations % Cv.cfg.every == 0 ? 1 : 0;
   if (n) {
     flag = D.flag_seq + 1;
     run_dense_integrate(c, d, n, pose34, seq, flag, c->stream);
@@ -1413,6 +1416,7 @@ uint32_t dense_queue(fmx_ctx* c, const float4* d, size_t n, const double* pose34
     std::memset(D.h_res.p, 0, 5 * sizeof(uint32_t));
   }
   D.seq_scan.push_back(scan_idx);
+  D.integrations++;
   return flag;
 }
 // A queued carve: wait for its completion word (the rays have then read the scan), take the counts.
@@ -2821,7 +2825,7 @@ fmx_status fmx_dense_integrate(fmx_ctx* c, const float* xyzw, size_t n, int src_
     if (D.voxels + n > D.max_voxels)
       throw StatusError(FMX_E_OOM, "dense map: " + std::to_string(D.voxels) + " voxels + " + std::to_string(n) +
                                        " points exceed max_voxels " + std::to_string(D.max_voxels));
-    if (D.seq_scan.size() >= 0xFFFFFFFEull) throw StatusError(FMX_E_STATE, "dense map: integration counter exhausted");
+    if (D.seq_scan.size() >= 0xFFFFFFFEull) throw StatusError(FMX_E_STATE, "dense map: owner numbering exhausted");
     const float4* d = reinterpret_cast<const float4*>(xyzw);
     if (n && !src_on_dev) {
       D.in.ensure(n);
@@ -2847,7 +2851,7 @@ fmx_status fmx_dense_stats(fmx_ctx* c, uint64_t out[4]) {
     const auto& D = c->dense;
     out[0] = D.voxels;
     out[1] = D.max_voxels;
-    out[2] = D.seq_scan.size();
+    out[2] = D.integrations;
     out[3] = D.slots;
   });
 }
@@ -2904,6 +2908,59 @@ fmx_status fmx_dense_download(fmx_ctx* c, uint32_t min_hits, double* xyz, uint64
   return fmx_carve_download(c, min_hits, 0, 0, &A, n);
 }
 
+fmx_status fmx_upload_voxels(fmx_ctx* c, const fmx_voxel_input* in, uint32_t n, fmx_upload_counts* counts) {
+  return guard<false>(c, [&] {
+    auto& D = c->dense;
+    auto& U = D.upload;
+    const char* why = "";
+    const fmx_status chk = upload_check(in, n, D.on, D.carve.have, &why);
+    if (chk != FMX_OK) throw StatusError(chk, why);
+    dense_settle(c);
+    if (counts) *counts = fmx_upload_counts{};
+    if (!n) return;
+    if (D.voxels + n > D.max_voxels)
+      throw StatusError(FMX_E_OOM, "dense map: " + std::to_string(D.voxels) + " voxels + " + std::to_string(n) +
+                                       " entries exceed max_voxels " + std::to_string(D.max_voxels));
+    // the owner numbers, the table's room for them and every buffer before anything is
+    // launched or changed (FMX_E_OOM when one cannot be had)
+    UploadOwners own;
+    if (!upload_owners(in->scan, n, D.seq_scan.size(), &own))
+      throw StatusError(FMX_E_STATE, "dense map: owner numbering exhausted");
+    D.seq_scan.reserve(D.seq_scan.size() + own.scans.size());
+    const auto up_ensure = [](auto& b, size_t m) { roll_ensure(b, m, "dense map upload"); };
+    up_ensure(U.cnt, 4);
+    up_ensure(U.xyz, 3 * (size_t)n);
+    up_ensure(U.owner, n);
+    up_ensure(U.slot, n);
+    if (in->index) up_ensure(U.index, n);
+    if (in->hits) up_ensure(U.hits, n);
+    if (in->misses) up_ensure(U.misses, n);
+    try {
+      U.h_cnt.ensure(4);
+    } catch (const HipError&) {
+      (void)hipGetLastError();
+      throw StatusError(FMX_E_OOM, "dense map upload: pinned host allocation failed");
+    }
+    const auto put = [&](void* dst, const void* src, size_t bytes) {
+      if (src) FMX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    };
+    put(U.xyz.p, in->xyz, 3 * (size_t)n * sizeof(double));
+    put(U.owner.p, own.owner.data(), (size_t)n * sizeof(uint32_t));
+    put(U.index.p, in->index, (size_t)n * sizeof(uint32_t));
+    put(U.hits.p, in->hits, (size_t)n * sizeof(uint32_t));
+    put(U.misses.p, in->misses, (size_t)n * sizeof(uint32_t));
+    // (within the reserved room; before the launches, so that no tag ever names an owner the table lacks)
+    D.seq_scan.insert(D.seq_scan.end(), own.scans.begin(), own.scans.end());
+    D.used = true;  // the configuration is final, as after an integration
+    run_dense_upload(c, n, in->index != nullptr, in->hits != nullptr, in->misses != nullptr, own.temp, c->stream);
+    FMX_HIP(hipMemcpyAsync(U.h_cnt.p, U.cnt.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns the arrays again (own.owner too)
+    const uint32_t invalid = U.h_cnt.p[0], oor = U.h_cnt.p[1], added = U.h_cnt.p[2];
+    D.voxels += added;
+    if (counts) *counts = fmx_upload_counts{added, n - invalid - oor - added, oor, invalid};
+  });
+}
+
 fmx_status fmx_dense_clear(fmx_ctx* c) {
   return guard<false>(c, [&] {
     auto& D = c->dense;
@@ -2912,6 +2969,7 @@ fmx_status fmx_dense_clear(fmx_ctx* c) {
     run_dense_clear(c, c->stream);
     D.voxels = 0;
     D.seq_scan.clear();
+    D.integrations = 0;
     D.roll.have_centre = false;  // (the spill holds scan_idx values: it stays)
   });
 }

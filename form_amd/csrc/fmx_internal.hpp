@@ -21,6 +21,7 @@
 #include "carve_host.hpp"
 #include "pair_sort_plan.hpp"
 #include "probe_host.hpp"
+#include "upload_host.hpp"
 #include "stage.hpp"
 
 namespace fmx {
@@ -594,7 +595,11 @@ struct fmx_ctx {
     uint32_t flag_seq = 0;         // the completion word's last value
     uint32_t pending = 0;          // ... of an integration queued and not yet waited for (else 0)
     uint64_t voxels = 0;           // occupied slots (host copy, current between integrations)
-    std::vector<uint64_t> seq_scan;  // integration number (a tag's high word) -> the caller's scan_idx
+    // owner number (a tag's high word) -> the caller's scan_idx.  One rising sequence since the
+    // last clear: an integration takes the next number, an upload one per distinct scan value
+    // (upload_host.hpp), so a later owner's tag is always the larger one
+    std::vector<uint64_t> seq_scan;
+    uint64_t integrations = 0;     // integrations since the last clear (fmx_dense_stats; the carve's `every` counts these)
     fmx::DBuf<float4> in;          // device copy of a host scan (fmx_dense_integrate)
     fmx::DBuf<float4> keep;        // register path: a host-announced scan, kept past the next one's DMA
     // download: slots counted, then appended
@@ -649,6 +654,16 @@ struct fmx_ctx {
       fmx::DBuf<unsigned long long> cnt;  // points: {absent, filtered, solid, out_of_range, invalid}; rays: {hit,
                                           // clear, out_of_range, invalid, steps}; zeroed by each call
     } probe;
+    // loading voxels back (fmx_upload_voxels; densemap.hip, the upload block): the device copies
+    // of a call's entries, grown at first use; nothing below is allocated, and nothing
+    // launched, unless that entry point is called
+    struct Upload {
+      fmx::DBuf<double> xyz;
+      fmx::DBuf<uint32_t> owner, index, hits, misses;  // owner: each entry's owner number (upload_host.hpp)
+      fmx::DBuf<uint32_t> slot;      // per entry: its slot (bit 31: it is its voxel's representative), or the dropped marker
+      fmx::DBuf<uint32_t> cnt;       // {invalid, out_of_range, added}; zeroed by each call
+      fmx::HBuf<uint32_t> h_cnt;
+    } upload;
   } dense;
 
   // ---- window keypoint store + maps
@@ -1035,6 +1050,13 @@ void run_probe_rays(fmx_ctx* c, const float4* d_pts, size_t n, const double* pos
 // voxel total set (two launches, one when kept is 0; queued)
 void run_roll_count(fmx_ctx* c, const long long cc[3], const uint32_t half[3], uint32_t out[2], hipStream_t st);
 void run_roll_rebuild(fmx_ctx* c, const long long cc[3], const uint32_t half[3], uint32_t kept, uint32_t evicted,
+                      hipStream_t st);
+// ... loading voxels back: the n > 0 entries staged in c->dense.upload (xyz, owner; index, hits
+// and misses where have_index / have_hits / have_misses, else 0, 1 and 0 per entry) into the table under the
+// temporary owner number temp (the caller has checked the capacity rule and sized every
+// buffer); {invalid, out_of_range, added} reach c->dense.upload.cnt and the device's voxel
+// total grows by `added` (three launches, queued)
+void run_dense_upload(fmx_ctx* c, uint32_t n, bool have_index, bool have_hits, bool have_misses, uint32_t temp,
                       hipStream_t st);
 // packed x, y, z (a staged host scan) -> float4 points with pad 0, on stream st
 void unpack_xyz(fmx_ctx* c, const float* d_packed, float4* d_out, size_t n, hipStream_t st);

@@ -114,6 +114,19 @@ class _VoxelArrays(C.Structure):
                 ("misses", C.c_void_p)]
 
 
+class _VoxelInput(C.Structure):
+    _fields_ = [("xyz", C.c_void_p), ("scan", C.c_void_p), ("index", C.c_void_p), ("hits", C.c_void_p),
+                ("misses", C.c_void_p)]
+
+
+class _UploadCounts(C.Structure):
+    _fields_ = [("added", C.c_uint32), ("merged", C.c_uint32), ("out_of_range", C.c_uint32), ("invalid", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(added=int(self.added), merged=int(self.merged), out_of_range=int(self.out_of_range),
+                    invalid=int(self.invalid))
+
+
 class _ProbePointCounts(C.Structure):
     _fields_ = [("absent", C.c_uint32), ("filtered", C.c_uint32), ("solid", C.c_uint32), ("out_of_range", C.c_uint32),
                 ("invalid", C.c_uint32)]
@@ -186,6 +199,7 @@ EXPORTED = [
     "fmx_carve_configure", "fmx_carve_rays", "fmx_carve_last", "fmx_carve_download", "fmx_carve_evict",
     "fmx_carve_drain",
     "fmx_probe_points", "fmx_probe_rays",
+    "fmx_upload_voxels",
 ]
 
 PAIR_SORT_FORMS = ("none", "per-block", "tail-scanned", "scatter-scanned")
@@ -207,6 +221,9 @@ def pair_sort_plan(n_planar: int, n_point: int, K: int, sorted: bool = True) -> 
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+_NO_ENTRIES = np.zeros(1, np.uint64)  # a non-NULL address for an array of no entries (never read)
 
 
 def _host(a):
@@ -919,6 +936,38 @@ class Context:
         del keep
         return dict(out, state=state, step=step, t=t, counts=cnt.as_dict())
 
+    # ---------------------------------------------------------------- loading voxels back
+    def dense_upload(self, points, scan=None, index=None, hits=None, misses=None) -> dict:
+        """fmx_upload_voxels: voxel records back into the map, under the keys dense_download,
+        roll_evict and roll_drain return them with (ctx.dense_upload(**ctx.roll_drain())):
+        points (N, 3) float64 in the world, scan (N,) uint64, index, hits and misses (N,)
+        uint32; None: 0, 0, 1 and 0 for every entry.  A resident voxel keeps its
+        representative and adds the hits and misses; an absent one is opened with the first
+        entry that names it.  misses needs carve_configure to have been called on this map.
+        Returns the counts (added, merged, out_of_range, invalid; they sum to N)."""
+        pts = np.ascontiguousarray(_host(points), np.float64)
+        if pts.size % 3 or (pts.ndim == 2 and pts.shape[1] != 3):
+            raise ValueError("points must be (N, 3)")
+        pts = pts.reshape(-1, 3)
+        n = len(pts)
+        keep = [pts]
+        A = _VoxelInput()
+        A.xyz = pts.ctypes.data if n else None
+        for name, a, dt in (("scan", scan, np.uint64), ("index", index, np.uint32), ("hits", hits, np.uint32),
+                            ("misses", misses, np.uint32)):
+            if a is None:
+                continue
+            a = np.ascontiguousarray(_host(a), dt).reshape(-1)
+            if len(a) != n:
+                raise ValueError(f"{name} must hold one value per point ({len(a)} != {n})")
+            keep.append(a)
+            # (an empty array still says that the field is given: misses on a map without carving is refused)
+            setattr(A, name, a.ctypes.data if n else _NO_ENTRIES.ctypes.data)
+        cnt = _UploadCounts()
+        self._chk(self._L.fmx_upload_voxels(self.h, C.byref(A), C.c_uint32(n), C.byref(cnt)))
+        del keep
+        return cnt.as_dict()
+
     def roll_stats(self) -> dict:
         s = np.zeros(6, np.uint64)
         self._chk(self._L.fmx_roll_stats(self.h, _p(s)))
@@ -1449,6 +1498,49 @@ class FORM:
         (Context.probe_rays; arguments as dense_lookup): the first solid voxel on each."""
         points, T = self._probe_args(points, pose)
         return self._est.probe_rays(points, T, min_hits, max_miss_ratio, skip)
+
+    def _need_dense(self):
+        if self._est is None or self._dense is None or not self._dense["enable"]:
+            raise RuntimeError("the dense map is off (set_dense_map, then initialize())")
+
+    def dense_restore(self, voxels: dict) -> dict:
+        """Put voxels back into the dense map (Context.dense_upload): what dense_map() and
+        dense_evicted() return, e.g. the evicted voxels of a place the sensor comes back to.
+        Returns the counts (added, merged, out_of_range, invalid)."""
+        self._need_dense()
+        v = dict(voxels)
+        return self._est.dense_upload(v["points"], v.get("scan"), v.get("index"), v.get("hits"), v.get("misses"))
+
+    def dense_save(self, path, min_hits: int = 1) -> None:
+        """Write the dense map to a numpy .npz: dense_map(min_hits)'s arrays (misses all 0
+        without set_dense_carve) and voxel_width."""
+        self._need_dense()
+        d = self.dense_map(min_hits)
+        misses = d["misses"] if "misses" in d else np.zeros(len(d["hits"]), np.uint32)
+        with open(path, "wb") as f:  # (np.savez would append .npz to a bare name)
+            np.savez(f, points=d["points"], scan=d["scan"], index=d["index"], hits=d["hits"], misses=misses,
+                     voxel_width=np.float64(self._dense["voxel_width"]))
+
+    def dense_load(self, path, drop_misses: bool = False) -> dict:
+        """Read a dense_save file into the map (dense_restore).  ValueError when the file's
+        voxel width is not, bit for bit, the configured one (the round trip promises
+        exactness), or when it holds non-zero misses and set_dense_carve is not on, unless
+        drop_misses.  Returns dense_restore's counts."""
+        self._need_dense()
+        with np.load(path) as z:
+            d = {k: z[k] for k in ("points", "scan", "index", "hits", "misses", "voxel_width")}
+        w = np.float64(d.pop("voxel_width"))
+        if w.tobytes() != np.float64(self._dense["voxel_width"]).tobytes():
+            raise ValueError(f"dense_load: the file's voxel width {float(w)!r} is not the configured "
+                             f"{self._dense['voxel_width']!r}")
+        carving = self._carve is not None and self._carve["enable"]
+        if not carving:
+            if d["misses"].any() and not drop_misses:
+                raise ValueError("dense_load: the file holds misses and carving is off (set_dense_carve, or drop_misses=True)")
+            del d["misses"]
+        elif drop_misses:
+            del d["misses"]
+        return self.dense_restore(d)
 
     def dense_evicted(self) -> dict:
         """The voxels the rolling map (set_dense_roll) has evicted since the last call, as

@@ -502,7 +502,8 @@ fmx_status fmx_dense_clear(fmx_ctx* ctx);
  * index, hits), the fields fmx_dense_download returns, go to the caller in no particular
  * order and the voxel leaves the table.  Every voxel inside stays, bit for bit.  Afterwards
  * `voxels` is the number kept and the capacity rule uses it; the integration counter is
- * unchanged; a later integration that sees an evicted voxel again opens it as a new voxel.
+ * unchanged; a later integration that sees an evicted voxel again opens it as a new voxel
+ * (fmx_upload_voxels, below, puts evicted voxels back first and so avoids that).
  * The content after a roll does not depend on the order the device's threads run in.
  * All of these: FMX_E_STATE unless the dense map is configured and enabled (fmx_roll_stats
  * excepted); FMX_E_INVAL for a null centre, a non-finite centre, a centre voxel out of
@@ -692,6 +693,60 @@ fmx_status fmx_probe_rays(fmx_ctx* ctx, const float* xyzw, size_t n_points, int 
                           const double pose34[12], uint32_t min_hits, uint32_t miss_num, uint32_t miss_den,
                           uint32_t skip, uint8_t* state, uint32_t* step, double* t,
                           const fmx_voxel_arrays* voxels, fmx_probe_ray_counts* counts);
+
+/* ---------------- loading voxels back into the dense voxel map -------------------
+ * The inverse of the downloads: voxel records, as fmx_carve_download, fmx_carve_evict and
+ * fmx_carve_drain hand them out, go back into the table (DESIGN.md §Dense map, Restoring).  A
+ * roll's spill can return when the sensor does, a map can be saved and resumed, two contexts'
+ * maps can be merged.  All arrays are host arrays of n entries; the semantics are exact and do
+ * not depend on the order the device's threads run in (tests/upload_ref.py restates them):
+ *   classes  entry i is invalid when a coordinate of xyz[i] is not finite, or hits is given and
+ *            hits[i] == 0 (a world point of exactly (0, 0, 0) is valid: the all-zero rule
+ *            belongs to sensor-frame points).  Otherwise its voxel is c_k = floor(xyz_k /
+ *            voxel_width) in fp64, the integration's expression, with no pose and no gate;
+ *            out_of_range unless every |c_k| < 2^20 - 1, tested in fp64 before the cast.  (A
+ *            representative was stored in the voxel it fell into: a downloaded point names
+ *            its own voxel again.)
+ *   resident the voxel is in the table: it keeps its representative (point, scan, index) bit
+ *            for bit, its hits grow by the sum of the entries' hits and its misses by the sum
+ *            of their misses; every such entry counts as merged.
+ *   absent   the voxel is opened and counts as added once.  Its representative is the entry
+ *            with the lowest input position among the valid entries of that voxel in this
+ *            call: xyz, scan and index are stored as given (any u64, any u32), hits and misses
+ *            are the sums over all of them; the other entries count as merged.  Spills kept
+ *            over time and concatenated in time order: the oldest owner wins.
+ * Sums are modulo 2^32, as the integration's.  An uploaded voxel behaves like any other from
+ * then on: integrations add to its hits, the carve may count misses on it (the upload never
+ * exempts it), rolls keep or evict it, downloads and probes return scan and index as given.
+ * An upload is not an integration: fmx_dense_stats' integration counter, the integration
+ * numbers that the carve's `every` counts, fmx_dense_last, fmx_carve_last, the roll's centre,
+ * its statistics and the spill are unchanged; fmx_dense_clear forgets uploaded voxels like
+ * all others.  The capacity rule is the integration's: FMX_E_OOM, nothing launched and
+ * nothing changed, unless voxels + n <= max_voxels.
+ * Status codes: FMX_E_STATE unless the dense map is configured and enabled; FMX_E_INVAL for
+ * in NULL, or xyz NULL with n > 0; FMX_E_STATE when misses is given and carving was never
+ * enabled on this map (there is no array to hold them); FMX_E_OOM by the capacity rule or
+ * when a per-call buffer cannot be allocated, FMX_E_STATE when the owner numbering (32 bits,
+ * one per integration and per distinct scan value of an upload since the last clear) would
+ * be exhausted: nothing changed in either case.  n == 0 succeeds with zero counts and
+ * launches nothing.  The call runs after whatever integration or roll is queued and returns
+ * once the counts are in.  A context that never calls it allocates and launches nothing for
+ * it. */
+typedef struct fmx_voxel_input {   /* fmx_voxel_arrays, read-only */
+  const double* xyz;       /* 3 n, required when n > 0 */
+  const uint64_t* scan;    /* NULL: 0 for every entry */
+  const uint32_t* index;   /* NULL: 0 */
+  const uint32_t* hits;    /* NULL: 1 */
+  const uint32_t* misses;  /* NULL: 0 */
+} fmx_voxel_input;
+typedef struct fmx_upload_counts {
+  uint32_t added;          /* new voxels */
+  uint32_t merged;         /* valid entries that did not become a representative */
+  uint32_t out_of_range;
+  uint32_t invalid;        /* the four sum to n */
+} fmx_upload_counts;
+fmx_status fmx_upload_voxels(fmx_ctx* ctx, const fmx_voxel_input* in, uint32_t n,
+                            fmx_upload_counts* counts /* may be NULL */);
 
 /* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
  * pose at the middle of the last registered sweep. */
