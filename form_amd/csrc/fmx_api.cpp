@@ -242,38 +242,40 @@ fmx_status guard(fmx_ctx* c, F&& f) {
   }
 }
 
+// Move every live scan's keypoints to the front of a fresh buffer (plan: store_plan.hpp).
 void compact_pool(fmx_ctx* c, int t) {
   Pool& pool = c->pool[t];
   DBuf<float4> npos, nnrm;
-  npos.ensure(pool.pos.cap);
-  if (t == 0) nnrm.ensure(pool.nrm.cap);
-  std::vector<std::pair<uint64_t, uint64_t>> order;  // (offset, scan)
-  for (auto& [s, r] : pool.ranges) order.push_back({r.first, s});
-  std::sort(order.begin(), order.end());
-  uint64_t o = 0;
-  for (auto& [off, s] : order) {
-    auto& r = pool.ranges[s];
-    if (r.second) {
-      FMX_HIP(hipMemcpyAsync(npos.p + o, pool.pos.p + off, r.second * sizeof(float4), hipMemcpyDeviceToDevice,
+  if (c->store_limits.pool) {
+    // under the test limit the pool compacts every few scans: same size again (ensure() on an
+    // empty buffer doubles what it is asked for, 2^k times the pool after k compactions)
+    npos.ensure_exact(pool.pos.cap);
+    if (t == 0) nnrm.ensure_exact(pool.nrm.cap);
+  } else {
+    npos.ensure(pool.pos.cap);
+    if (t == 0) nnrm.ensure(pool.nrm.cap);
+  }
+  const PoolPlan plan = plan_pool_compact(pool.ranges);
+  for (const StoreCopy& cp : plan.copies) {
+    FMX_HIP(hipMemcpyAsync(npos.p + cp.dst, pool.pos.p + cp.src, cp.n * sizeof(float4), hipMemcpyDeviceToDevice,
+                           c->stream));
+    if (t == 0)
+      FMX_HIP(hipMemcpyAsync(nnrm.p + cp.dst, pool.nrm.p + cp.src, cp.n * sizeof(float4), hipMemcpyDeviceToDevice,
                              c->stream));
-      if (t == 0)
-        FMX_HIP(hipMemcpyAsync(nnrm.p + o, pool.nrm.p + off, r.second * sizeof(float4), hipMemcpyDeviceToDevice,
-                               c->stream));
-    }
-    r.first = o;
-    o += r.second;
   }
   FMX_HIP(hipStreamSynchronize(c->stream));
   pool.pos = std::move(npos);  // frees the old pool
   if (t == 0) pool.nrm = std::move(nnrm);
-  pool.used = o;
+  pool.used = plan.used;
+  if (!c->store_limits.pool) pool.limit = pool.pos.cap;
+  ++pool.n_compact;
 }
 
 void ensure_pool_room(fmx_ctx* c, int t, uint64_t need) {
   Pool& pool = c->pool[t];
-  if (pool.used + need <= pool.pos.cap) return;
+  if (pool_has_room(pool.used, need, pool.limit)) return;
   compact_pool(c, t);
-  if (pool.used + need > pool.pos.cap)
+  if (!pool_has_room(pool.used, need, pool.limit))
     throw StatusError(FMX_E_OOM, "keypoint pool capacity exceeded (raise keypoint_pool_capacity)");
 }
 
@@ -288,13 +290,11 @@ void pool_add(fmx_ctx* c, int t, uint64_t scan, const float* f, uint32_t n) {
     pos[i] = make_float4(f[st * i], f[st * i + 1], f[st * i + 2], 0.f);
     if (t == 0) nrm[i] = make_float4(f[st * i + 3], f[st * i + 4], f[st * i + 5], 0.f);
   }
-  auto& rg = pool.ranges[scan];
-  if (rg.second == 0) rg.first = pool.used;
-  else if (rg.first + rg.second != pool.used) throw StatusError(FMX_E_STATE, "scan keypoints must be added contiguously");
-  FMX_HIP(hipMemcpy(pool.pos.p + pool.used, pos.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  if (t == 0) FMX_HIP(hipMemcpy(pool.nrm.p + pool.used, nrm.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  rg.second += n;
-  pool.used += n;
+  const uint64_t at = pool.used;
+  if (!pool_append(pool.ranges, pool.used, scan, n))
+    throw StatusError(FMX_E_STATE, "scan keypoints must be added contiguously");
+  FMX_HIP(hipMemcpy(pool.pos.p + at, pos.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  if (t == 0) FMX_HIP(hipMemcpy(pool.nrm.p + at, nrm.data(), n * sizeof(float4), hipMemcpyHostToDevice));
 }
 
 // device float4 arrays -> pool under `scan`
@@ -302,14 +302,12 @@ void pool_add_device(fmx_ctx* c, int t, uint64_t scan, const float* pos4, const 
   if (n == 0) return;
   ensure_pool_room(c, t, n);
   Pool& pool = c->pool[t];
-  auto& rg = pool.ranges[scan];
-  if (rg.second == 0) rg.first = pool.used;
-  else if (rg.first + rg.second != pool.used) throw StatusError(FMX_E_STATE, "scan keypoints must be added contiguously");
-  FMX_HIP(hipMemcpyAsync(pool.pos.p + pool.used, pos4, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  const uint64_t at = pool.used;
+  if (!pool_append(pool.ranges, pool.used, scan, n))
+    throw StatusError(FMX_E_STATE, "scan keypoints must be added contiguously");
+  FMX_HIP(hipMemcpyAsync(pool.pos.p + at, pos4, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
   if (t == 0)
-    FMX_HIP(hipMemcpyAsync(pool.nrm.p + pool.used, nrm4, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-  rg.second += n;
-  pool.used += n;
+    FMX_HIP(hipMemcpyAsync(pool.nrm.p + at, nrm4, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
 }
 
 // The current query set now holds scan `scan`'s features: nothing matched so far applies.
@@ -1996,6 +1994,13 @@ fmx_status fmx_create(const fmx_params* p, int device, fmx_ctx** out) {
     c->pool[0].pos.ensure(cap);
     c->pool[0].nrm.ensure(cap);
     c->pool[1].pos.ensure(cap);
+    // test-only store limits (store_plan.hpp); read per context, so that a process can hold
+    // contexts with and without them
+    c->store_limits = parse_store_limits(std::getenv("FMX_TEST_STORE_LIMITS"));
+    for (int t = 0; t < 2; ++t) {
+      const uint64_t alloc = c->pool[t].pos.cap;
+      c->pool[t].limit = c->store_limits.pool ? std::min<uint64_t>(c->store_limits.pool, alloc) : alloc;
+    }
   });
   if (st != FMX_OK) {
     fmx_destroy(c);
@@ -3240,7 +3245,11 @@ fmx_status fmx_map_download(fmx_ctx* c, double voxel_width, double* planar, uint
 fmx_status fmx_last_stats(fmx_ctx* c, uint64_t* stats, int n) {
   return guard<false>(c, [&] {
     if (!stats || n < 0) throw StatusError(FMX_E_INVAL, "null stats");
-    for (int k = 0; k < n; ++k) stats[k] = k < kStatsN ? c->stats[k] : 0;
+    // the stores' events since fmx_create: counted under every entry point, not per scan
+    const uint64_t store[kStatsStoreN] = {c->pool[0].n_compact, c->pool[1].n_compact, c->win.n_compact,
+                                          c->win.n_grow_pl, c->win.n_grow_pt};
+    for (int k = 0; k < n; ++k)
+      stats[k] = k < kStatsN ? c->stats[k] : k < kStatsN + kStatsStoreN ? store[k - kStatsN] : 0;
   });
 }
 

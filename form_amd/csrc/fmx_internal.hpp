@@ -23,6 +23,7 @@
 #include "probe_host.hpp"
 #include "upload_host.hpp"
 #include "stage.hpp"
+#include "store_plan.hpp"
 
 namespace fmx {
 
@@ -88,9 +89,18 @@ struct DBuf {
     // at least 256k elements (<= 8 MB for the widest element): the per-scan buffers of
     // a 128 x 2048 stream never regrow once the window has filled (a regrowth's
     // hipFree serializes the device mid-scan)
-    size_t c = std::max<size_t>(2 * n + 64, (size_t)1 << 18);
+    size_t c = dbuf_alloc_elems(n);  // store_plan.hpp
     FMX_HIP(hipMalloc(&p, c * sizeof(T)));
     cap = c;
+  }
+  // exactly n elements, no geometric head room: for a buffer that replaces one of a known
+  // size (the pool under FMX_TEST_STORE_LIMITS, whose every compaction takes a fresh buffer)
+  void ensure_exact(size_t n) {
+    if (n <= cap) return;
+    ++dbuf_reallocs();
+    release();
+    FMX_HIP(hipMalloc(&p, n * sizeof(T)));
+    cap = n;
   }
   void release() {
     if (p) (void)hipFree(p);
@@ -296,7 +306,9 @@ struct Pool {
   DBuf<float4> pos, nrm;  // nrm unused for point features
   bool planar = true;
   uint64_t used = 0;
-  std::map<uint64_t, std::pair<uint64_t, uint32_t>> ranges;  // scan -> (offset, count)
+  uint64_t limit = 0;  // records the pool takes: pos.cap, or less under FMX_TEST_STORE_LIMITS
+  uint64_t n_compact = 0;  // compactions since context creation (fmx_last_stats)
+  PoolRanges ranges;  // scan -> (offset, count)
 };
 
 // One built voxel map (VoxelMap<P>, map.hpp:66-94) in HBM, both feature types
@@ -359,21 +371,14 @@ struct WinPosesN {
   double m[N][12];
 };
 using WinPoses = WinPosesN<kWinMaxArgPoses>;
-struct WinPair {  // one FeatureFactor(X(i), X(j))'s rows in the arena
-  uint64_t i, j;
-  uint64_t pl_off, pt_off;
-  uint32_t pl_n, pt_n;
-};
-struct WinSeg {  // scan j's correspondences (the last match of its ICP loop)
-  uint64_t pl_off = 0, pt_off = 0;
-  uint32_t pl_n = 0, pt_n = 0;
-  std::vector<WinPair> pairs;  // i ascending
-};
+// WinPair, WinSeg: store_plan.hpp (with the store's host-side planning)
 struct WinStore {
   DBuf<double> pl[2], pt[2];  // ping-pong arenas: plane [9][cap_pl], point [6][cap_pt]
   int cur = 0;
   uint64_t cap_pl = 0, cap_pt = 0, tail_pl = 0, tail_pt = 0;
-  std::map<uint64_t, WinSeg> segs;
+  WinSegs segs;
+  bool exact_pl = false, exact_pt = false;  // FMX_TEST_STORE_LIMITS: that capacity is used as asked
+  uint64_t n_compact = 0, n_grow_pl = 0, n_grow_pt = 0;  // since context creation (fmx_last_stats)
   // uploaded pair set (win_set_pairs)
   DBuf<uint32_t> meta;  // [chunks (4 words each)][chunk_range]
   const Chunk* chunks_p = nullptr;
@@ -462,7 +467,8 @@ struct ExLaunch {
 
 }  // namespace fmx
 
-constexpr int kStatsN = 14;  // fmx_last_stats entries
+constexpr int kStatsN = 14;  // fmx_last_stats entries of the last registered scan ...
+constexpr int kStatsStoreN = 5;  // ... followed by the stores' cumulative event counts
 
 struct fmx_ctx {
   fmx_ctx() = default;
@@ -668,6 +674,7 @@ struct fmx_ctx {
 
   // ---- window keypoint store + maps
   fmx::Pool pool[2];
+  fmx::StoreLimits store_limits;  // FMX_TEST_STORE_LIMITS as read by fmx_create (all 0: production sizes)
   fmx::VoxMap map;  // both feature types
   std::vector<uint64_t> map_scans;  // pair k -> scan id
   fmx::DBuf<fmx::Seg> segs[2];

@@ -3138,7 +3138,7 @@ void run_insert(fmx_ctx* c, uint64_t scan, uint32_t* n_inserted) {
   for (int t = 0; t < 2; ++t) {
     const uint32_t nq = t == 0 ? c->n_qpl : c->n_qpt;
     if (tot[t] > nq) throw StatusError(FMX_E_HIP, "implausible insert total");
-    if (c->pool[t].used + tot[t] > c->pool[t].pos.cap) throw StatusError(FMX_E_OOM, "keypoint pool capacity exceeded");
+    if (!pool_has_room(c->pool[t].used, tot[t], c->pool[t].limit)) throw StatusError(FMX_E_OOM, "keypoint pool capacity exceeded");
   }
   InsArgs ia;
   ia.nq_pl = c->n_qpl;
@@ -3159,11 +3159,8 @@ void run_insert(fmx_ctx* c, uint64_t scan, uint32_t* n_inserted) {
   }
   for (int t = 0; t < 2; ++t) {
     Pool& pool = c->pool[t];
-    auto& rg = pool.ranges[scan];
-    if (rg.second == 0) rg.first = pool.used;
-    else if (rg.first + rg.second != pool.used) throw StatusError(FMX_E_STATE, "non-contiguous insert for scan");
-    rg.second += tot[t];
-    pool.used += tot[t];
+    if (!pool_append(pool.ranges, pool.used, scan, tot[t]))
+      throw StatusError(FMX_E_STATE, "non-contiguous insert for scan");
   }
   if (n_inserted) {
     n_inserted[0] = tot[0];

@@ -697,18 +697,7 @@ void win_persist(fmx_ctx* c, uint64_t j) {
     npt += c->m.cnt_pt[k];
   }
   win_reserve(c, npl, npt);
-  WinSeg s;
-  s.pl_off = W.tail_pl;
-  s.pt_off = W.tail_pt;
-  s.pl_n = (uint32_t)npl;
-  s.pt_n = (uint32_t)npt;
-  uint64_t op = 0, ot = 0;
-  for (uint32_t k = 0; k < c->K; ++k) {
-    if (c->m.cnt_pl[k] + c->m.cnt_pt[k] > 0)
-      s.pairs.push_back(WinPair{c->map_scans[k], j, s.pl_off + op, s.pt_off + ot, c->m.cnt_pl[k], c->m.cnt_pt[k]});
-    op += c->m.cnt_pl[k];
-    ot += c->m.cnt_pt[k];
-  }
+  WinSeg s = win_make_seg(j, W.tail_pl, W.tail_pt, c->map_scans.data(), c->m.cnt_pl.data(), c->m.cnt_pt.data(), c->K);
   rows_copy(st, c->m.c_pl.p, c->m.ld_pl, 0, W.pl[W.cur].p, W.cap_pl, s.pl_off, (uint32_t)npl, c->m.c_pt.p, c->m.ld_pt, 0,
             W.pt[W.cur].p, W.cap_pt, s.pt_off, (uint32_t)npt);
   W.tail_pl += npl;
@@ -717,52 +706,39 @@ void win_persist(fmx_ctx* c, uint64_t j) {
 }
 
 // Room for (npl, npt) more rows at the tail: compact the live segments into the other
-// arena (growing both when the live rows fill more than half of it).
+// arena (growing both when the live rows fill more than half of it).  The plan, with the
+// rebased segment and pair offsets, is store_plan.hpp's; the copies run here.
 void win_reserve(fmx_ctx* c, uint64_t npl, uint64_t npt) {
   WinStore& W = c->win;
   hipStream_t st = c->stream;
   if (W.cap_pl == 0) {
-    W.cap_pl = std::max<uint64_t>(c->P.keypoint_pool_capacity, 1u << 20);
-    W.cap_pt = std::max<uint64_t>(W.cap_pl / 4, 1u << 18);
+    W.exact_pl = c->store_limits.win_pl != 0;
+    W.exact_pt = c->store_limits.win_pt != 0;
+    uint64_t want_pl, want_pt;
+    win_initial_caps(c->P.keypoint_pool_capacity, c->store_limits, want_pl, want_pt);
     for (int b = 0; b < 2; ++b) {
-      W.pl[b].ensure(9 * W.cap_pl);
-      W.pt[b].ensure(6 * W.cap_pt);
+      W.pl[b].ensure(9 * want_pl);
+      W.pt[b].ensure(6 * want_pt);
     }
-    W.cap_pl = W.pl[0].cap / 9;  // DBuf over-allocates: use it
-    W.cap_pt = W.pt[0].cap / 6;
+    W.cap_pl = win_cap_of(want_pl, W.pl[0].cap, 9, W.exact_pl);  // DBuf over-allocates: use it
+    W.cap_pt = win_cap_of(want_pt, W.pt[0].cap, 6, W.exact_pt);
   }
-  if (W.tail_pl + npl <= W.cap_pl && W.tail_pt + npt <= W.cap_pt) return;
-  uint64_t live_pl = npl, live_pt = npt;
-  for (auto& [j, s] : W.segs) {
-    live_pl += s.pl_n;
-    live_pt += s.pt_n;
-  }
+  const WinPlan plan = plan_win_reserve(W.segs, W.tail_pl, W.tail_pt, W.cap_pl, W.cap_pt, npl, npt);
+  if (!plan.compact) return;
   const int nxt = 1 - W.cur;
-  uint64_t cap_pl = W.cap_pl, cap_pt = W.cap_pt;
-  while (2 * live_pl > cap_pl) cap_pl *= 2;
-  while (2 * live_pt > cap_pt) cap_pt *= 2;
-  if (cap_pl != W.cap_pl || cap_pt != W.cap_pt) {  // grow: both arenas (contents move below)
-    W.pl[nxt].ensure(9 * cap_pl);
-    W.pt[nxt].ensure(6 * cap_pt);
+  const bool grow_pl = plan.want_pl != W.cap_pl, grow_pt = plan.want_pt != W.cap_pt;
+  if (grow_pl || grow_pt) {  // grow: both arenas (contents move below)
+    W.pl[nxt].ensure(9 * plan.want_pl);
+    W.pt[nxt].ensure(6 * plan.want_pt);
   }
-  const uint64_t ncap_pl = cap_pl != W.cap_pl ? W.pl[nxt].cap / 9 : W.cap_pl;
-  const uint64_t ncap_pt = cap_pt != W.cap_pt ? W.pt[nxt].cap / 6 : W.cap_pt;
-  uint64_t tpl = 0, tpt = 0;
-  for (auto& [j, s] : W.segs) {
-    rows_copy(st, W.pl[W.cur].p, W.cap_pl, s.pl_off, W.pl[nxt].p, ncap_pl, tpl, s.pl_n, W.pt[W.cur].p, W.cap_pt,
-              s.pt_off, W.pt[nxt].p, ncap_pt, tpt, s.pt_n);
-    for (auto& p : s.pairs) {
-      p.pl_off = p.pl_off - s.pl_off + tpl;
-      p.pt_off = p.pt_off - s.pt_off + tpt;
-    }
-    s.pl_off = tpl;
-    s.pt_off = tpt;
-    tpl += s.pl_n;
-    tpt += s.pt_n;
-  }
+  const uint64_t ncap_pl = grow_pl ? win_cap_of(plan.want_pl, W.pl[nxt].cap, 9, W.exact_pl) : W.cap_pl;
+  const uint64_t ncap_pt = grow_pt ? win_cap_of(plan.want_pt, W.pt[nxt].cap, 6, W.exact_pt) : W.cap_pt;
+  for (size_t k = 0; k < plan.pl.size(); ++k)
+    rows_copy(st, W.pl[W.cur].p, W.cap_pl, plan.pl[k].src, W.pl[nxt].p, ncap_pl, plan.pl[k].dst, (uint32_t)plan.pl[k].n,
+              W.pt[W.cur].p, W.cap_pt, plan.pt[k].src, W.pt[nxt].p, ncap_pt, plan.pt[k].dst, (uint32_t)plan.pt[k].n);
   W.cur = nxt;
-  W.tail_pl = tpl;
-  W.tail_pt = tpt;
+  W.tail_pl = plan.tail_pl;
+  W.tail_pt = plan.tail_pt;
   if (ncap_pl != W.cap_pl || ncap_pt != W.cap_pt) {  // the old arena grows too (free space only)
     W.pl[1 - nxt].ensure(9 * ncap_pl);
     W.pt[1 - nxt].ensure(6 * ncap_pt);
@@ -770,16 +746,16 @@ void win_reserve(fmx_ctx* c, uint64_t npl, uint64_t npt) {
   W.cap_pl = ncap_pl;
   W.cap_pt = ncap_pt;
   W.chunks_valid = false;
+  ++W.n_compact;
+  W.n_grow_pl += grow_pl;
+  W.n_grow_pt += grow_pt;
 }
 
 // KeypointMap / ConstraintManager erase of scan s (constraints.cpp:195-203): its
 // segment and every pair (s, j) of the other segments.  Rows stay until compaction.
 void win_remove(fmx_ctx* c, uint64_t s) {
   WinStore& W = c->win;
-  W.segs.erase(s);
-  for (auto& [j, seg] : W.segs)
-    seg.pairs.erase(std::remove_if(seg.pairs.begin(), seg.pairs.end(), [&](const WinPair& p) { return p.i == s; }),
-                    seg.pairs.end());
+  win_erase_scan(W.segs, s);
   W.chunks_valid = false;
 }
 

@@ -998,7 +998,10 @@ class Context:
     def last_stats(self) -> dict:
         keys = ["icp_iters", "lm_iters", "matched_planar", "matched_point", "map_planar", "map_point",
                 "linearizations", "map_scans", "host_waits", "spec_matches", "spec_hits", "spec_map",
-                "pipelined", "window_poses"]
+                "pipelined", "window_poses",
+                # cumulative since the context was created (every entry point counts)
+                "pool_compactions_planar", "pool_compactions_point", "win_compactions", "win_growths_plane",
+                "win_growths_point"]
         s = np.zeros(len(keys), np.uint64)
         self._chk(self._L.fmx_last_stats(self.h, _p(s), C.c_int(len(keys))))
         return {k: int(v) for k, v in zip(keys, s)}

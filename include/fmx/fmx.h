@@ -772,7 +772,12 @@ fmx_status fmx_map_download(fmx_ctx* ctx, double voxel_width, double* planar, ui
  * the one built speculatively during the previous scan's final LM, 0 when built at
  * the start of this scan), pipelined (1 when the scan's features were extracted
  * during the previous registration, fmx_next_scan), window_poses (poses in the
- * smoother's window after the scan: the host LM's system is 6 x window_poses)};
+ * smoother's window after the scan: the host LM's system is 6 x window_poses)},
+ * followed by five counts since fmx_create that every entry point advances, the seam API's
+ * fmx_keypoints_add and fmx_map_insert included: {pool_compactions_planar,
+ * pool_compactions_point (the keypoint pool moved its live scans to a fresh buffer),
+ * win_compactions (the smoothing-mode window store moved its live rows to its other
+ * arena), win_growths_plane, win_growths_point (... into a larger one)};
  * entries past the known ones read 0. */
 fmx_status fmx_last_stats(fmx_ctx* ctx, uint64_t* stats, int n);
 /* Work of the last fmx_match (counted by the kernel, available while profiling is
