@@ -804,6 +804,172 @@ __global__ __launch_bounds__(kDenseThreads) void k_probe_rays(const float4* __re
   }
 }
 
+// ---- nearest (DESIGN.md §Dense map, Nearest; include/fmx/fmx.h, fmx_nearest_voxels).  The
+// nearest solid representative in the cube of cells around a point's own voxel.  Read only, one
+// launch per call on the context stream, as the probes.
+//
+// A group of FMX_NEAREST_LANES adjacent lanes serves one point.  The cube is enumerated by
+// Chebyshev shell s = max |d_k| from the offset list (nearest_host.hpp: sorted by shell, built
+// once by the host, 4 B per cell, resident in the caches); the lanes of a group stride through
+// a shell's cells.  Which cells a point examines does not depend on what the table holds, so a
+// lane issues FMX_NEAREST_AHEAD home-slot key loads back to back and then examines them: hits
+// on a key match only, misses only under a ratio filter (dense_take), the representative only
+// for a solid voxel.  Each lane keeps its best (d2 bits, key, slot); d2 >= 0, so its bit
+// pattern orders like its value, and the pair is reduced lexicographically over the group by an
+// xor butterfly after every shell s >= 1 and after the last one.  The order of visits plays no
+// part: the minimum of a set is the same however it is split.
+//
+// Early stop: after shell s >= 1 a group is done once its best d2, or max_dist2, is below
+// (1 - 2^-20) (s w)^2: every cell of a later shell differs from the own voxel by s + 1 or more
+// on one axis, so its representative is farther than (s - 2^-32) w on that axis and its
+// computed d2 is strictly larger than that bound (DESIGN.md has the derivation): neither the
+// minimum nor a tie can change.  FMX_NEAREST_STOP=0 builds the form that walks every shell.
+//
+// The shell loop is uniform over the wave (it ends when every group of the wave is done; a
+// done group idles), so every lane meets every shuffle.  No LDS, no scratch, no dynamically
+// indexed array.  The group's first lane writes the outputs and loads the winner's remaining
+// fields once; the counters get one return-less atomic per wave and counter (ballot +
+// popcount, the lookups a wave sum).
+#ifndef FMX_NEAREST_LANES
+#define FMX_NEAREST_LANES 4
+#endif
+#ifndef FMX_NEAREST_AHEAD
+#define FMX_NEAREST_AHEAD 4
+#endif
+#ifndef FMX_NEAREST_STOP
+#define FMX_NEAREST_STOP 1
+#endif
+static_assert(FMX_NEAREST_LANES >= 1 && FMX_NEAREST_LANES <= 64 && (FMX_NEAREST_LANES & (FMX_NEAREST_LANES - 1)) == 0,
+              "FMX_NEAREST_LANES is a power of two from 1 to 64");
+static_assert(FMX_NEAREST_AHEAD >= 1, "FMX_NEAREST_AHEAD is at least 1");
+#ifndef FMX_NEAREST_BLOCKS
+#define FMX_NEAREST_BLOCKS 2048
+#endif
+constexpr int kNearestBlocks = FMX_NEAREST_BLOCKS;  // the grid's cap: a grid stride beyond it
+
+// cnt: {found, none, out_of_range, invalid, lookups}.  o.t takes dist2; o.step is not used.
+__global__ __launch_bounds__(kDenseThreads) void k_nearest(const float4* __restrict__ pts, uint32_t n, DenseArgs a,
+                                                           DenseTake tk, uint32_t reach, double max_d2,
+                                                           const uint32_t* __restrict__ offs,
+                                                           const unsigned long long* __restrict__ keys,
+                                                           const unsigned long long* __restrict__ tags,
+                                                           const uint32_t* __restrict__ hits,
+                                                           const double* __restrict__ xyz, ProbeOut o,
+                                                           unsigned long long* __restrict__ cnt) {
+  constexpr uint32_t L = (uint32_t)FMX_NEAREST_LANES;
+  constexpr int kLimit = (1 << 20) - 1;
+  // Grid stride over the groups (64-bit: n * L may pass 2^32), uniform over the wave: it runs
+  // while the wave's first group has a point.  The grid is capped (kNearestBlocks) so that the
+  // counters' atomics, all on five words, are few: one per wave and launch, not per point group.
+  const unsigned long long stride = (unsigned long long)gridDim.x * (unsigned long long)kDenseThreads / L;
+  const unsigned long long g0 = ((unsigned long long)blockIdx.x * (unsigned long long)kDenseThreads + threadIdx.x) / L;
+  const unsigned long long w0 = ((unsigned long long)blockIdx.x * (unsigned long long)kDenseThreads + (threadIdx.x & ~63u)) / L;
+  const uint32_t gl = threadIdx.x & (L - 1u);  // the lane's place in its group
+  const unsigned long long inf_bits = 0x7FF0000000000000ull;
+  unsigned long long looked = 0;
+  uint32_t n_found = 0, n_none = 0, n_oor = 0, n_inv = 0;  // (the same in every lane of the wave)
+  for (unsigned long long it = 0; w0 + it < (unsigned long long)n; it += stride) {
+    const unsigned long long q = g0 + it;
+    int cls = -1;  // past the end
+    double p0 = 0.0, p1 = 0.0, p2 = 0.0;
+    int c0 = 0, c1 = 0, c2 = 0;
+    if (q < (unsigned long long)n) {
+      double wp[3];
+      int v[3];
+      cls = probe_classify(pts[q], a, wp, v);
+      p0 = wp[0], p1 = wp[1], p2 = wp[2];
+      if (cls == 0) c0 = v[0], c1 = v[1], c2 = v[2];
+    }
+    bool done = cls != 0;
+    unsigned long long b_bits = inf_bits, b_key = kDenseEmpty;  // (no stored key is all ones)
+    uint32_t b_slot = kDenseDropped;
+    for (uint32_t s = 0; s <= reach; ++s) {
+      if (!__any(!done)) break;  // (the whole wave)
+      if (!done) {
+        const uint32_t lo = s ? (2u * s - 1u) * (2u * s - 1u) * (2u * s - 1u) : 0u, hi = (2u * s + 1u) * (2u * s + 1u) * (2u * s + 1u);
+        for (uint32_t base = lo + gl; base < hi; base += L * (uint32_t)FMX_NEAREST_AHEAD) {
+          unsigned long long key[FMX_NEAREST_AHEAD], k0[FMX_NEAREST_AHEAD];
+          uint32_t h0[FMX_NEAREST_AHEAD];
+          bool ok[FMX_NEAREST_AHEAD];
+#pragma unroll
+          for (int u = 0; u < FMX_NEAREST_AHEAD; ++u) {
+            const uint32_t at = base + (uint32_t)u * L;
+            // (at < hi <= (2 reach + 1)^3, the list's length: the host checked the reach)
+            const uint32_t od = at < hi ? offs[at] : 0u;
+            const int x = c0 + (int)(od & 255u) - FMX_NEAREST_MAX_REACH, y = c1 + (int)((od >> 8) & 255u) - FMX_NEAREST_MAX_REACH,
+                      z = c2 + (int)((od >> 16) & 255u) - FMX_NEAREST_MAX_REACH;
+            // a cell that cannot be stored is skipped (each coordinate + bias is then a 21-bit field)
+            ok[u] = at < hi && abs(x) < kLimit && abs(y) < kLimit && abs(z) < kLimit;
+            key[u] = dense_key(x, y, z);
+            h0[u] = (uint32_t)mix64(key[u]) & a.slot_mask;
+            k0[u] = ok[u] ? keys[h0[u]] : kDenseEmpty;
+            looked += ok[u] ? 1ull : 0ull;
+          }
+#pragma unroll
+          for (int u = 0; u < FMX_NEAREST_AHEAD; ++u) {
+            if (ok[u]) {
+              const uint32_t slot = probe_find(key[u], h0[u], k0[u], keys, a.slot_mask);
+              if (slot != kDenseDropped && dense_take(tk, hits[slot], slot)) {
+                const double e0 = xyz[3 * (size_t)slot + 0] - p0, e1 = xyz[3 * (size_t)slot + 1] - p1,
+                             e2 = xyz[3 * (size_t)slot + 2] - p2;
+                const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+                const unsigned long long bits = (unsigned long long)__double_as_longlong(d2);
+                if (d2 <= max_d2 && (bits < b_bits || (bits == b_bits && key[u] < b_key))) {
+                  b_bits = bits;
+                  b_key = key[u];
+                  b_slot = slot;
+                }
+              }
+            }
+          }
+        }
+      }
+      if (s == 0 && reach != 0) continue;  // (uniform: the own cell alone certifies nothing)
+      // the group's best in every lane of it (a done group repeats its own: harmless)
+#pragma unroll
+      for (uint32_t x = 1; x < L; x <<= 1) {
+        const unsigned long long ob = __shfl_xor(b_bits, (int)x, 64), ok2 = __shfl_xor(b_key, (int)x, 64);
+        const uint32_t os = (uint32_t)__shfl_xor((int)b_slot, (int)x, 64);
+        if (ob < b_bits || (ob == b_bits && ok2 < b_key)) {
+          b_bits = ob;
+          b_key = ok2;
+          b_slot = os;
+        }
+      }
+#if FMX_NEAREST_STOP
+      if (s >= 1) {
+        const double sw = (double)s * a.w;
+        const double lim = (1.0 - 0x1p-20) * (sw * sw);
+        if (__longlong_as_double((long long)b_bits) < lim || max_d2 < lim) done = true;
+      }
+#endif
+    }
+    int st = -1;
+    if (cls >= 0 && gl == 0) {
+      const bool found = cls == 0 && b_key != kDenseEmpty;
+      st = cls == 1 ? FMX_PROBE_INVALID : cls == 3 ? FMX_PROBE_OUT_OF_RANGE : found ? FMX_PROBE_SOLID : FMX_PROBE_ABSENT;
+      const uint32_t i = (uint32_t)q;
+      o.state[i] = (uint8_t)st;
+      if (o.t) o.t[i] = __longlong_as_double((long long)(found ? b_bits : inf_bits));
+      const uint32_t slot = found ? b_slot : kDenseDropped;
+      probe_store(o, i, slot, (found && o.hits) ? hits[slot] : 0u, tk, tags, xyz);
+    }
+    // (a wave meets fewer than 2^32 points in all: n is below that)
+    n_found += (uint32_t)__popcll(__ballot(st == FMX_PROBE_SOLID));
+    n_none += (uint32_t)__popcll(__ballot(st == FMX_PROBE_ABSENT));
+    n_oor += (uint32_t)__popcll(__ballot(st == FMX_PROBE_OUT_OF_RANGE));
+    n_inv += (uint32_t)__popcll(__ballot(st == FMX_PROBE_INVALID));
+  }
+  const unsigned long long w_looked = wave_sum(looked);
+  if ((threadIdx.x & 63) == 0) {  // results unused: return-less
+    if (n_found) atomicAdd(&cnt[0], (unsigned long long)n_found);
+    if (n_none) atomicAdd(&cnt[1], (unsigned long long)n_none);
+    if (n_oor) atomicAdd(&cnt[2], (unsigned long long)n_oor);
+    if (n_inv) atomicAdd(&cnt[3], (unsigned long long)n_inv);
+    if (w_looked) atomicAdd(&cnt[4], w_looked);
+  }
+}
+
 // ---- loading voxels back (DESIGN.md §Dense map, Restoring; include/fmx/fmx.h,
 // fmx_upload_voxels).  The inverse of the downloads: entries (world point, owner number, index,
 // hits, misses), staged by the host, go into the table.  Three launches on one stream, the
@@ -1035,6 +1201,30 @@ void run_probe_rays(fmx_ctx* c, const float4* d_pts, size_t n, const double* pos
   ProfScope ps(c->prof, PROF_DENSE, (double)n * (16.0 + probe_out_bytes(o)), st);
   hipLaunchKernelGGL(k_probe_rays, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)n, a,
                      probe_take_args(c, f), skip, D.keys.p, D.tags.p, D.hits.p, D.xyz.p, o, D.probe.cnt.p);
+  FMX_HIP(hipGetLastError());
+}
+
+void run_nearest(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, const ProbeFilter& f, uint32_t reach,
+                 double max_dist2, const ProbeOut& o, hipStream_t st) {
+  auto& D = c->dense;
+  auto& N = D.nearest;
+  if (!N.have) {  // the cube's offsets in shell order, once per context (the host copy outlives the transfer)
+    FMX_HIP(hipMemcpyAsync(N.offs.p, N.h_offs.data(), N.h_offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    N.have = true;
+  }
+  const DenseArgs a = dense_args(c, pose34);
+  // one group of lanes per point up to kNearestBlocks blocks (8 waves on every SIMD of 256 CUs), a grid
+  // stride beyond: the counters' same-address atomics, one per wave, bound the launch otherwise
+  const unsigned long long want = ((unsigned long long)n * FMX_NEAREST_LANES + kDenseThreads - 1) / kDenseThreads;
+  const uint32_t blocks = (uint32_t)(want < (unsigned long long)kNearestBlocks ? want : (unsigned long long)kNearestBlocks);
+  FMX_HIP(hipMemsetAsync(D.probe.cnt.p, 0, 8 * sizeof(unsigned long long), st));
+  // DESIGN.md §Dense map, Nearest: the point (16), the own cell's key word (8) and what is
+  // written per point; the other cells' 8 B per lookup, + 4 (+ 4 under a ratio) per present
+  // voxel and + 24 per solid one, are not known at launch and not counted (the call's own
+  // `lookups` gives the first)
+  ProfScope ps(c->prof, PROF_DENSE, (double)n * (24.0 + probe_out_bytes(o)), st);
+  hipLaunchKernelGGL(k_nearest, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)n, a, probe_take_args(c, f),
+                     reach, max_dist2, N.offs.p, D.keys.p, D.tags.p, D.hits.p, D.xyz.p, o, D.probe.cnt.p);
   FMX_HIP(hipGetLastError());
 }
 

@@ -1631,6 +1631,71 @@ void probe_call(fmx_ctx* c, bool rays, const float* xyzw, size_t n, int src_on_d
     throw StatusError(FMX_E_STATE, "probe: a voxel's tag names an integration the context does not know");
 }
 
+// ---- nearest (fmx_nearest_voxels; densemap.hip, the nearest block; nearest_host.hpp)
+// probe_call's pattern: the checks, the per-call buffers (the probe's, dist2 in t), one
+// launch, the copies out.  cnt: found, none, out_of_range, invalid, lookups.
+void nearest_call(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double* pose34, uint32_t min_hits,
+                  uint32_t miss_num, uint32_t miss_den, uint32_t reach, double max_dist2, uint8_t* state, double* dist2,
+                  const fmx_voxel_arrays* voxels, unsigned long long cnt[5]) {
+  auto& D = c->dense;
+  auto& P = D.probe;
+  auto& N = D.nearest;
+  if (!D.on) throw StatusError(FMX_E_STATE, "the dense map is not enabled (fmx_dense_configure)");
+  const char* why = "";
+  const fmx_status chk = nearest_check(xyzw, (unsigned long long)n, pose34, reach, max_dist2, &why);
+  if (chk != FMX_OK) throw StatusError(chk, why);
+  dense_settle(c);
+  for (int k = 0; k < 5; ++k) cnt[k] = 0;
+  if (!n) return;
+  const fmx_voxel_arrays A = voxels ? *voxels : fmx_voxel_arrays{};
+  const bool want_tag = A.scan || A.index;
+  // every buffer before anything is launched or written (FMX_E_OOM when one cannot be had)
+  const auto ensure = [](auto& b, size_t m) { roll_ensure(b, m, "dense map nearest"); };
+  if (!N.have && N.h_offs.empty()) N.h_offs = nearest_offsets(FMX_NEAREST_MAX_REACH);
+  ensure(N.offs, N.h_offs.size());
+  ensure(P.cnt, 8);
+  ensure(P.state, n);
+  if (dist2) ensure(P.t, n);
+  if (want_tag) ensure(P.tag, n);
+  if (A.hits) ensure(P.hits, n);
+  if (A.misses) ensure(P.misses, n);
+  if (A.xyz) ensure(P.xyz, 3 * n);
+  if (!src_on_dev) ensure(D.in, n);
+  std::vector<uint8_t> own_state;
+  std::vector<unsigned long long> tag;
+  if (want_tag) {
+    tag.resize(n);
+    if (!state) own_state.resize(n);
+  }
+  uint8_t* h_state = state ? state : (want_tag ? own_state.data() : nullptr);
+  const float4* d = reinterpret_cast<const float4*>(xyzw);
+  if (!src_on_dev) {
+    FMX_HIP(hipMemcpyAsync(D.in.p, xyzw, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    d = D.in.p;
+  }
+  const ProbeOut o{P.state.p,
+                   nullptr,
+                   dist2 ? P.t.p : nullptr,
+                   want_tag ? P.tag.p : nullptr,
+                   A.hits ? P.hits.p : nullptr,
+                   A.misses ? P.misses.p : nullptr,
+                   A.xyz ? P.xyz.p : nullptr};
+  run_nearest(c, d, n, pose34, probe_filter(min_hits, miss_num, miss_den), reach, max_dist2, o, c->stream);
+  const auto out = [&](void* dst, const void* src, size_t bytes) {
+    if (dst) FMX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  };
+  out(cnt, P.cnt.p, 5 * sizeof(unsigned long long));
+  out(h_state, P.state.p, n);
+  out(dist2, P.t.p, n * sizeof(double));
+  out(want_tag ? tag.data() : nullptr, P.tag.p, n * sizeof(unsigned long long));
+  out(A.hits, P.hits.p, n * sizeof(uint32_t));
+  out(A.misses, P.misses.p, n * sizeof(uint32_t));
+  out(A.xyz, P.xyz.p, 3 * n * sizeof(double));
+  FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns the points again
+  if (want_tag && !probe_resolve(h_state, tag.data(), n, D.seq_scan, A.scan, A.index))
+    throw StatusError(FMX_E_STATE, "nearest: a voxel's tag names an integration the context does not know");
+}
+
 // dsk_cells (fmx_register_cloud with deskewing on): the scan's per-cell sweep fractions
 void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feature_counts* out,
                    const float* dsk_cells = nullptr) {
@@ -3165,6 +3230,17 @@ fmx_status fmx_probe_rays(fmx_ctx* c, const float* xyzw, size_t n, int src_on_de
     unsigned long long k[5];
     probe_call(c, true, xyzw, n, src_on_dev, pose34, min_hits, miss_num, miss_den, skip, state, step, t, voxels, k);
     if (counts) *counts = fmx_probe_ray_counts{(uint32_t)k[0], (uint32_t)k[1], (uint32_t)k[2], (uint32_t)k[3], k[4]};
+  });
+}
+
+// ---- the nearest solid voxel (densemap.hip, the nearest block; nearest_host.hpp)
+fmx_status fmx_nearest_voxels(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double pose34[12],
+                              uint32_t min_hits, uint32_t miss_num, uint32_t miss_den, uint32_t reach, double max_dist2,
+                              uint8_t* state, double* dist2, const fmx_voxel_arrays* voxels, fmx_nearest_counts* counts) {
+  return guard<false>(c, [&] {
+    unsigned long long k[5];
+    nearest_call(c, xyzw, n, src_on_dev, pose34, min_hits, miss_num, miss_den, reach, max_dist2, state, dist2, voxels, k);
+    if (counts) *counts = fmx_nearest_counts{(uint32_t)k[0], (uint32_t)k[1], (uint32_t)k[2], (uint32_t)k[3], k[4]};
   });
 }
 

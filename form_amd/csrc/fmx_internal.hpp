@@ -21,6 +21,7 @@
 #include "carve_host.hpp"
 #include "pair_sort_plan.hpp"
 #include "probe_host.hpp"
+#include "nearest_host.hpp"
 #include "upload_host.hpp"
 #include "stage.hpp"
 #include "store_plan.hpp"
@@ -660,6 +661,15 @@ struct fmx_ctx {
       fmx::DBuf<unsigned long long> cnt;  // points: {absent, filtered, solid, out_of_range, invalid}; rays: {hit,
                                           // clear, out_of_range, invalid, steps}; zeroed by each call
     } probe;
+    // nearest (fmx_nearest_voxels; densemap.hip, the nearest block): the cube's offsets in shell
+    // order (nearest_host.hpp), built at first use; the per-call outputs are the probe's
+    // buffers above (dist2 in t).  Nothing here is allocated, and nothing launched, unless
+    // that entry point is called
+    struct Nearest {
+      bool have = false;
+      std::vector<uint32_t> h_offs;
+      fmx::DBuf<uint32_t> offs;
+    } nearest;
     // loading voxels back (fmx_upload_voxels; densemap.hip, the upload block): the device copies
     // of a call's entries, grown at first use; nothing below is allocated, and nothing
     // launched, unless that entry point is called
@@ -1051,6 +1061,12 @@ void run_probe_points(fmx_ctx* c, const float4* d_pts, size_t n, const double* p
                       const ProbeOut& o, hipStream_t st);
 void run_probe_rays(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, const ProbeFilter& f,
                     uint32_t skip, const ProbeOut& o, hipStream_t st);
+// ... nearest: per point the nearest solid representative among the cells within `reach` of its
+// own voxel with d2 <= max_dist2 (o.t takes d2, o.step is not used; the counts go to
+// c->dense.probe.cnt as above: found, none, out_of_range, invalid, lookups).  The caller has
+// allocated c->dense.nearest.offs; its content is sent once (one launch, queued; reads only)
+void run_nearest(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, const ProbeFilter& f, uint32_t reach,
+                 double max_dist2, const ProbeOut& o, hipStream_t st);
 // ... rolling: {inside, outside} of the box of voxels |v - cc| <= half (one launch, waits for
 // it); then, with c->dense.o_* sized to `evicted` and c->dense.roll.s_* to `kept`, the evicted
 // voxels appended to o_*, the kept ones put back into the emptied table and the device's

@@ -145,9 +145,31 @@ class _ProbeRayCounts(C.Structure):
                     invalid=int(self.invalid), steps=int(self.steps))
 
 
+class _NearestCounts(C.Structure):
+    _fields_ = [("found", C.c_uint32), ("none", C.c_uint32), ("out_of_range", C.c_uint32), ("invalid", C.c_uint32),
+                ("lookups", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(found=int(self.found), none=int(self.none), out_of_range=int(self.out_of_range),
+                    invalid=int(self.invalid), lookups=int(self.lookups))
+
+
+NEAREST_MAX_REACH = 8  # FMX_NEAREST_MAX_REACH
+
 # fmx_probe_points / fmx_probe_rays: the per-point state
 PROBE_ABSENT, PROBE_FILTERED, PROBE_SOLID, PROBE_OUT_OF_RANGE, PROBE_INVALID = range(5)
 PROBE_NO_STEP = 0xFFFFFFFF
+
+
+def fitness_of(state, dist2) -> dict:
+    """FORM.dense_fitness's figures from a nearest_voxels result's state and dist2."""
+    state = np.asarray(state)
+    found = state == PROBE_SOLID
+    n_valid = int(found.sum() + (state == PROBE_ABSENT).sum())
+    n_found = int(found.sum())
+    total = math.fsum(float(d) for d in np.asarray(dist2, np.float64)[found])  # in index order
+    return dict(n_valid=n_valid, n_found=n_found, fitness=n_found / n_valid if n_valid else 0.0,
+                rmse=math.sqrt(total / n_found) if n_found else 0.0)
 
 
 def miss_fraction(max_miss_ratio):
@@ -200,6 +222,7 @@ EXPORTED = [
     "fmx_carve_drain",
     "fmx_probe_points", "fmx_probe_rays",
     "fmx_upload_voxels",
+    "fmx_nearest_voxels",
 ]
 
 PAIR_SORT_FORMS = ("none", "per-block", "tail-scanned", "scatter-scanned")
@@ -936,6 +959,33 @@ class Context:
         del keep
         return dict(out, state=state, step=step, t=t, counts=cnt.as_dict())
 
+    # ---------------------------------------------------------------- the nearest solid voxel
+    def nearest_voxels(self, points, pose34, reach: int = 1, max_dist=None, min_hits: int = 1,
+                       max_miss_ratio=None) -> dict:
+        """fmx_nearest_voxels: per (N, 4) float32 point (numpy, or a torch tensor on the host or
+        the device) at pose34 the nearest solid representative among the cells within `reach`
+        (at most NEAREST_MAX_REACH) of its own voxel, no farther than max_dist (None: no
+        limit; max_dist2 = max_dist * max_dist); changes nothing.  Returns state (N,) uint8
+        (PROBE_SOLID: found; PROBE_ABSENT: none; _OUT_OF_RANGE, _INVALID), dist2 (N,) float64
+        (the squared distance, +inf unless found), the winner's points, scan, index, hits and
+        misses (zeros unless found) and counts (found, none, out_of_range, invalid, lookups:
+        the cells the kernel looked up).  With reach = floor(max_dist / voxel_width) + 1 it is
+        an exact radius search."""
+        num, den = miss_fraction(max_miss_ratio)
+        md = math.inf if max_dist is None else float(max_dist)
+        on_dev, ptr, n, keep = _scan_ptr(points)
+        pose = np.ascontiguousarray(pose34, np.float64).reshape(12)
+        if on_dev:
+            _ready(keep)
+        A, out = self._voxel_arrays(n, True)
+        state, dist2 = np.zeros(n, np.uint8), np.zeros(n, np.float64)
+        cnt = _NearestCounts()
+        self._chk(self._L.fmx_nearest_voxels(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev), _p(pose),
+                                             C.c_uint32(min_hits), C.c_uint32(num), C.c_uint32(den), C.c_uint32(reach),
+                                             C.c_double(md * md), _p(state), _p(dist2), C.byref(A), C.byref(cnt)))
+        del keep
+        return dict(out, state=state, dist2=dist2, counts=cnt.as_dict())
+
     # ---------------------------------------------------------------- loading voxels back
     def dense_upload(self, points, scan=None, index=None, hits=None, misses=None) -> dict:
         """fmx_upload_voxels: voxel records back into the map, under the keys dense_download,
@@ -1501,6 +1551,28 @@ class FORM:
         (Context.probe_rays; arguments as dense_lookup): the first solid voxel on each."""
         points, T = self._probe_args(points, pose)
         return self._est.probe_rays(points, T, min_hits, max_miss_ratio, skip)
+
+    def dense_nearest(self, points, radius_m: float, pose=None, min_hits: int = 1, max_miss_ratio=None) -> dict:
+        """The exact radius search of the dense map (Context.nearest_voxels; points and pose as
+        dense_lookup): per point the nearest solid voxel no farther than radius_m, or none.
+        reach = floor(radius_m / voxel_width) + 1; ValueError when that passes
+        NEAREST_MAX_REACH."""
+        points, T = self._probe_args(points, pose)
+        r = float(radius_m)
+        if not (r >= 0.0) or math.isinf(r):
+            raise ValueError("radius_m must be a finite number >= 0")
+        reach = math.floor(r / float(self._dense["voxel_width"])) + 1
+        if reach > NEAREST_MAX_REACH:
+            raise ValueError(f"radius_m spans more than {NEAREST_MAX_REACH} voxels: reach {reach}")
+        return self._est.nearest_voxels(points, T, reach, r, min_hits, max_miss_ratio)
+
+    def dense_fitness(self, points, radius_m: float, pose=None, min_hits: int = 1, max_miss_ratio=None) -> dict:
+        """A scan judged against the dense map, from dense_nearest on the host: n_valid (points
+        neither invalid nor out of range), n_found (those with a solid voxel within radius_m),
+        fitness = n_found / n_valid (0.0 when there are none) and rmse = sqrt(sum(dist2 of the
+        found) / n_found) (0.0 when there are none), summed in index order with math.fsum."""
+        got = self.dense_nearest(points, radius_m, pose, min_hits, max_miss_ratio)
+        return fitness_of(got["state"], got["dist2"])
 
     def _need_dense(self):
         if self._est is None or self._dense is None or not self._dense["enable"]:

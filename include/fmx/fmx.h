@@ -748,6 +748,63 @@ typedef struct fmx_upload_counts {
 fmx_status fmx_upload_voxels(fmx_ctx* ctx, const fmx_voxel_input* in, uint32_t n,
                             fmx_upload_counts* counts /* may be NULL */);
 
+/* ---------------- the nearest solid voxel of the dense map: radius search -------------
+ * How far is the nearest surface from a point, and which voxel is it: answered on the device
+ * without a download (DESIGN.md §Dense map, Nearest).  The call only reads: the table, the
+ * counters, fmx_dense_stats, fmx_dense_last, fmx_carve_last, the spill and the estimator are as
+ * before.  All of it is exact, fp64 without contraction, one rounding per written operation
+ * (tests/nearest_ref.py restates it):
+ *   point    the classes of fmx_probe_points, word for word: invalid by the integration's rule;
+ *            otherwise the world point p is the integration's expression and the own voxel
+ *            c_k = floor(p_k / voxel_width); out_of_range unless every |c_k| < 2^20 - 1, tested
+ *            in fp64 before the cast.  The dense gate plays no part;
+ *   filter   fmx_carve_download's rule, as for the probes: solid iff hits >= max(min_hits, 1)
+ *            and, when miss_den != 0, misses * miss_den <= hits * miss_num in 64-bit integers.
+ *            misses reads 0 on a map that never enabled carving;
+ *   cube     the candidates are the cells c + d with every |d_k| <= reach.  A cell with a
+ *            coordinate outside |.| < 2^20 - 1 cannot be stored and is skipped; every other is
+ *            looked up find-only.  A present and solid voxel with representative q has
+ *            e_k = q_k - p_k and d2 = (e_0 * e_0 + e_1 * e_1) + e_2 * e_2, and is admitted iff
+ *            d2 <= max_dist2 (+inf: no limit; 0: coincident points only);
+ *   winner   the admitted candidate with the smallest d2; among equal d2 the one with the
+ *            smallest packed key ((c_0 + 2^20) << 42 | (c_1 + 2^20) << 21 | c_2 + 2^20) as u64;
+ *   outputs  host arrays aligned with the input.  state[i] is FMX_PROBE_SOLID (found),
+ *            FMX_PROBE_ABSENT (none), FMX_PROBE_OUT_OF_RANGE or FMX_PROBE_INVALID, never
+ *            FMX_PROBE_FILTERED.  dist2[i] is the winner's d2, +inf for every other state.  The
+ *            winner's five voxel fields are returned, zeros otherwise; scan is the scan_idx of
+ *            the owner of the voxel.  Any pointer may be NULL (voxels NULL: all five of its
+ *            pointers NULL) and is then neither computed into nor copied.
+ * What a result certifies.  A representative lies in the cell its key names up to the one
+ * rounding of floor(x / voxel_width), for an integrated and for an uploaded voxel alike, so a
+ * voxel outside the cube is farther than (reach - 2^-32) * voxel_width from p: a result with
+ * d2 below the square of that is the nearest solid representative of the whole map.  A call
+ * with max_dist2 = r * r and reach = floor(r / voxel_width) + 1 is therefore an exact radius
+ * search: the nearest solid representative within r, or none.
+ * counts->lookups is the number of cells the kernel looked up, summed over the points: a
+ * diagnostic for the cost model that depends on what the kernel may skip (a finished shell s >=
+ * 1 ends a point's search once the best d2, or max_dist2, is below (1 - 2^-20) (s w)^2).  It is
+ * at least the number of valid in-range points and at most the number of storable cube cells
+ * of those points; the outputs and the four class counts are the definition's whatever is
+ * skipped.
+ * Status codes: FMX_E_STATE unless the dense map is configured and enabled; FMX_E_INVAL for a
+ * NULL or non-finite pose, NULL points with n_points > 0, n_points >= 2^32, reach >
+ * FMX_NEAREST_MAX_REACH, or a NaN or negative max_dist2; FMX_E_OOM, nothing written, when a
+ * per-call buffer cannot be allocated.  n_points == 0 succeeds with zero counts and launches
+ * nothing.  The call runs after whatever integration or roll is queued and returns once the
+ * outputs are in.  A context that never calls it allocates and launches nothing for it. */
+#define FMX_NEAREST_MAX_REACH 8
+typedef struct fmx_nearest_counts {
+  uint32_t found;
+  uint32_t none;
+  uint32_t out_of_range;
+  uint32_t invalid;          /* the four sum to n */
+  uint64_t lookups;          /* cells the kernel looked up: a diagnostic, see above */
+} fmx_nearest_counts;
+fmx_status fmx_nearest_voxels(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                              const double pose34[12], uint32_t min_hits, uint32_t miss_num, uint32_t miss_den,
+                              uint32_t reach, double max_dist2, uint8_t* state, double* dist2,
+                              const fmx_voxel_arrays* voxels, fmx_nearest_counts* counts);
+
 /* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
  * pose at the middle of the last registered sweep. */
 fmx_status fmx_current_pose(fmx_ctx* ctx, double pose34[12]);
