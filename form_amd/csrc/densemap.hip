@@ -847,6 +847,86 @@ static_assert(FMX_NEAREST_AHEAD >= 1, "FMX_NEAREST_AHEAD is at least 1");
 #endif
 constexpr int kNearestBlocks = FMX_NEAREST_BLOCKS;  // the grid's cap: a grid stride beyond it
 
+// One point group's search, the per-trip body shared by k_nearest and k_align: the shell loop,
+// the look-ahead loads, the group butterfly and the early stop, as described above.  cls: the
+// point's class (0: in range, p its world point and c its own voxel; anything else: no point
+// to search for, the group idles); gl: the lane's place in
+// its group of L.  On return every lane of the group holds the group's best (b_bits, b_key,
+// b_slot), untouched when nothing was admitted; `looked` has grown by this lane's lookups.
+// Every lane of the wave calls it, a group without a point idling: the loop is wave-uniform.
+template <uint32_t L>
+__device__ __forceinline__ void nearest_search(int cls, double p0, double p1, double p2, int c0, int c1, int c2,
+                                               uint32_t gl, const DenseArgs& a, const DenseTake& tk, uint32_t reach,
+                                               double max_d2, const uint32_t* __restrict__ offs,
+                                               const unsigned long long* __restrict__ keys,
+                                               const uint32_t* __restrict__ hits, const double* __restrict__ xyz,
+                                               unsigned long long& b_bits, unsigned long long& b_key, uint32_t& b_slot,
+                                               unsigned long long& looked) {
+  constexpr int kLimit = (1 << 20) - 1;
+  bool done = cls != 0;
+  for (uint32_t s = 0; s <= reach; ++s) {
+    if (!__any(!done)) break;  // (the whole wave)
+    if (!done) {
+      const uint32_t lo = s ? (2u * s - 1u) * (2u * s - 1u) * (2u * s - 1u) : 0u, hi = (2u * s + 1u) * (2u * s + 1u) * (2u * s + 1u);
+      for (uint32_t base = lo + gl; base < hi; base += L * (uint32_t)FMX_NEAREST_AHEAD) {
+        unsigned long long key[FMX_NEAREST_AHEAD], k0[FMX_NEAREST_AHEAD];
+        uint32_t h0[FMX_NEAREST_AHEAD];
+        bool ok[FMX_NEAREST_AHEAD];
+#pragma unroll
+        for (int u = 0; u < FMX_NEAREST_AHEAD; ++u) {
+          const uint32_t at = base + (uint32_t)u * L;
+          // (at < hi <= (2 reach + 1)^3, the list's length: the host checked the reach)
+          const uint32_t od = at < hi ? offs[at] : 0u;
+          const int x = c0 + (int)(od & 255u) - FMX_NEAREST_MAX_REACH, y = c1 + (int)((od >> 8) & 255u) - FMX_NEAREST_MAX_REACH,
+                    z = c2 + (int)((od >> 16) & 255u) - FMX_NEAREST_MAX_REACH;
+          // a cell that cannot be stored is skipped (each coordinate + bias is then a 21-bit field)
+          ok[u] = at < hi && abs(x) < kLimit && abs(y) < kLimit && abs(z) < kLimit;
+          key[u] = dense_key(x, y, z);
+          h0[u] = (uint32_t)mix64(key[u]) & a.slot_mask;
+          k0[u] = ok[u] ? keys[h0[u]] : kDenseEmpty;
+          looked += ok[u] ? 1ull : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < FMX_NEAREST_AHEAD; ++u) {
+          if (ok[u]) {
+            const uint32_t slot = probe_find(key[u], h0[u], k0[u], keys, a.slot_mask);
+            if (slot != kDenseDropped && dense_take(tk, hits[slot], slot)) {
+              const double e0 = xyz[3 * (size_t)slot + 0] - p0, e1 = xyz[3 * (size_t)slot + 1] - p1,
+                           e2 = xyz[3 * (size_t)slot + 2] - p2;
+              const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+              const unsigned long long bits = (unsigned long long)__double_as_longlong(d2);
+              if (d2 <= max_d2 && (bits < b_bits || (bits == b_bits && key[u] < b_key))) {
+                b_bits = bits;
+                b_key = key[u];
+                b_slot = slot;
+              }
+            }
+          }
+        }
+      }
+    }
+    if (s == 0 && reach != 0) continue;  // (uniform: the own cell alone certifies nothing)
+    // the group's best in every lane of it (a done group repeats its own: harmless)
+#pragma unroll
+    for (uint32_t x = 1; x < L; x <<= 1) {
+      const unsigned long long ob = __shfl_xor(b_bits, (int)x, 64), ok2 = __shfl_xor(b_key, (int)x, 64);
+      const uint32_t os = (uint32_t)__shfl_xor((int)b_slot, (int)x, 64);
+      if (ob < b_bits || (ob == b_bits && ok2 < b_key)) {
+        b_bits = ob;
+        b_key = ok2;
+        b_slot = os;
+      }
+    }
+#if FMX_NEAREST_STOP
+    if (s >= 1) {
+      const double sw = (double)s * a.w;
+      const double lim = (1.0 - 0x1p-20) * (sw * sw);
+      if (__longlong_as_double((long long)b_bits) < lim || max_d2 < lim) done = true;
+    }
+#endif
+  }
+}
+
 // cnt: {found, none, out_of_range, invalid, lookups}.  o.t takes dist2; o.step is not used.
 __global__ __launch_bounds__(kDenseThreads) void k_nearest(const float4* __restrict__ pts, uint32_t n, DenseArgs a,
                                                            DenseTake tk, uint32_t reach, double max_d2,
@@ -857,7 +937,6 @@ __global__ __launch_bounds__(kDenseThreads) void k_nearest(const float4* __restr
                                                            const double* __restrict__ xyz, ProbeOut o,
                                                            unsigned long long* __restrict__ cnt) {
   constexpr uint32_t L = (uint32_t)FMX_NEAREST_LANES;
-  constexpr int kLimit = (1 << 20) - 1;
   // Grid stride over the groups (64-bit: n * L may pass 2^32), uniform over the wave: it runs
   // while the wave's first group has a point.  The grid is capped (kNearestBlocks) so that the
   // counters' atomics, all on five words, are few: one per wave and launch, not per point group.
@@ -880,70 +959,10 @@ __global__ __launch_bounds__(kDenseThreads) void k_nearest(const float4* __restr
       p0 = wp[0], p1 = wp[1], p2 = wp[2];
       if (cls == 0) c0 = v[0], c1 = v[1], c2 = v[2];
     }
-    bool done = cls != 0;
     unsigned long long b_bits = inf_bits, b_key = kDenseEmpty;  // (no stored key is all ones)
     uint32_t b_slot = kDenseDropped;
-    for (uint32_t s = 0; s <= reach; ++s) {
-      if (!__any(!done)) break;  // (the whole wave)
-      if (!done) {
-        const uint32_t lo = s ? (2u * s - 1u) * (2u * s - 1u) * (2u * s - 1u) : 0u, hi = (2u * s + 1u) * (2u * s + 1u) * (2u * s + 1u);
-        for (uint32_t base = lo + gl; base < hi; base += L * (uint32_t)FMX_NEAREST_AHEAD) {
-          unsigned long long key[FMX_NEAREST_AHEAD], k0[FMX_NEAREST_AHEAD];
-          uint32_t h0[FMX_NEAREST_AHEAD];
-          bool ok[FMX_NEAREST_AHEAD];
-#pragma unroll
-          for (int u = 0; u < FMX_NEAREST_AHEAD; ++u) {
-            const uint32_t at = base + (uint32_t)u * L;
-            // (at < hi <= (2 reach + 1)^3, the list's length: the host checked the reach)
-            const uint32_t od = at < hi ? offs[at] : 0u;
-            const int x = c0 + (int)(od & 255u) - FMX_NEAREST_MAX_REACH, y = c1 + (int)((od >> 8) & 255u) - FMX_NEAREST_MAX_REACH,
-                      z = c2 + (int)((od >> 16) & 255u) - FMX_NEAREST_MAX_REACH;
-            // a cell that cannot be stored is skipped (each coordinate + bias is then a 21-bit field)
-            ok[u] = at < hi && abs(x) < kLimit && abs(y) < kLimit && abs(z) < kLimit;
-            key[u] = dense_key(x, y, z);
-            h0[u] = (uint32_t)mix64(key[u]) & a.slot_mask;
-            k0[u] = ok[u] ? keys[h0[u]] : kDenseEmpty;
-            looked += ok[u] ? 1ull : 0ull;
-          }
-#pragma unroll
-          for (int u = 0; u < FMX_NEAREST_AHEAD; ++u) {
-            if (ok[u]) {
-              const uint32_t slot = probe_find(key[u], h0[u], k0[u], keys, a.slot_mask);
-              if (slot != kDenseDropped && dense_take(tk, hits[slot], slot)) {
-                const double e0 = xyz[3 * (size_t)slot + 0] - p0, e1 = xyz[3 * (size_t)slot + 1] - p1,
-                             e2 = xyz[3 * (size_t)slot + 2] - p2;
-                const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
-                const unsigned long long bits = (unsigned long long)__double_as_longlong(d2);
-                if (d2 <= max_d2 && (bits < b_bits || (bits == b_bits && key[u] < b_key))) {
-                  b_bits = bits;
-                  b_key = key[u];
-                  b_slot = slot;
-                }
-              }
-            }
-          }
-        }
-      }
-      if (s == 0 && reach != 0) continue;  // (uniform: the own cell alone certifies nothing)
-      // the group's best in every lane of it (a done group repeats its own: harmless)
-#pragma unroll
-      for (uint32_t x = 1; x < L; x <<= 1) {
-        const unsigned long long ob = __shfl_xor(b_bits, (int)x, 64), ok2 = __shfl_xor(b_key, (int)x, 64);
-        const uint32_t os = (uint32_t)__shfl_xor((int)b_slot, (int)x, 64);
-        if (ob < b_bits || (ob == b_bits && ok2 < b_key)) {
-          b_bits = ob;
-          b_key = ok2;
-          b_slot = os;
-        }
-      }
-#if FMX_NEAREST_STOP
-      if (s >= 1) {
-        const double sw = (double)s * a.w;
-        const double lim = (1.0 - 0x1p-20) * (sw * sw);
-        if (__longlong_as_double((long long)b_bits) < lim || max_d2 < lim) done = true;
-      }
-#endif
-    }
+    nearest_search<L>(cls, p0, p1, p2, c0, c1, c2, gl, a, tk, reach, max_d2, offs, keys, hits, xyz, b_bits, b_key, b_slot,
+                      looked);
     int st = -1;
     if (cls >= 0 && gl == 0) {
       const bool found = cls == 0 && b_key != kDenseEmpty;
@@ -967,6 +986,161 @@ __global__ __launch_bounds__(kDenseThreads) void k_nearest(const float4* __restr
     if (n_oor) atomicAdd(&cnt[2], (unsigned long long)n_oor);
     if (n_inv) atomicAdd(&cnt[3], (unsigned long long)n_inv);
     if (w_looked) atomicAdd(&cnt[4], w_looked);
+  }
+}
+
+// ---- aligning (DESIGN.md §Dense map, Aligning; include/fmx/fmx.h, fmx_align_system).  The
+// nearest search fused with the point-to-point linearization against the winner: per launch
+// the packed 7 x 7 system of a scan at a pose (28 doubles + the error) and five counts, nothing
+// per point.  Read only, one launch per system on the context stream.
+//
+// A group of FMX_ALIGN_LANES adjacent lanes serves one kept point; group g has point
+// i = g * every (the points in between are skipped: never loaded), so a strided launch is dense
+// in lanes.  The search is nearest_search, the winner stays in registers; the group's first
+// lane loads the winner's representative q and adds the three rows of point_row<1> (X(i) the
+// identity, p_i = q, p_j the sensor-frame point) into 28 fp64 accumulators that persist over
+// the grid-stride trips.  The reduction is k_linearize_total's (linearize.hip): the wave's
+// reduce-scatter, the block's waves added in wave order through LDS, the block partial out with
+// agent-scope stores, an agent-scope ticket, the last block summing the partials in block
+// order and writing the system, and the counters, to mapped host memory behind the completion
+// word.  Every sum's order is fixed by n, every and the grid: the bits do not depend on the
+// order the lanes run in.  The class counts are one return-less atomic per wave and counter.
+#ifndef FMX_ALIGN_LANES
+#define FMX_ALIGN_LANES 1
+#endif
+static_assert(FMX_ALIGN_LANES >= 1 && FMX_ALIGN_LANES <= 64 && (FMX_ALIGN_LANES & (FMX_ALIGN_LANES - 1)) == 0,
+              "FMX_ALIGN_LANES is a power of two from 1 to 64");
+constexpr int kAlignWaves = kDenseThreads / kWave;
+constexpr int kAlignLd = 32;  // doubles per block partial (28 used)
+constexpr int kAlignOutCounts = 32;  // out[32..36]: the counters' bit patterns behind the 29 doubles
+
+namespace {
+#include "factor_rows.hpp"
+}  // namespace
+
+// m: the kept points, ceil(n / every).  cnt: {found, none, out_of_range, invalid, lookups},
+// zeroed by the caller.  ticket: 0 at launch, 0 again afterwards.  out: mapped host memory.
+__global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restrict__ pts, uint32_t m, uint32_t every,
+                                                         DenseArgs a, DenseTake tk, uint32_t reach, double max_d2,
+                                                         double inv, const uint32_t* __restrict__ offs,
+                                                         const unsigned long long* __restrict__ keys,
+                                                         const uint32_t* __restrict__ hits,
+                                                         const double* __restrict__ xyz,
+                                                         unsigned long long* __restrict__ cnt, double* __restrict__ bpart,
+                                                         uint32_t* __restrict__ ticket, double* __restrict__ out,
+                                                         uint32_t* __restrict__ flag, uint32_t seq) {
+  constexpr uint32_t L = (uint32_t)FMX_ALIGN_LANES;
+  constexpr int NG = 28;
+  constexpr int kGroups = kDenseThreads / NG;  // final reduction: lane groups x 28 entries
+  const unsigned long long stride = (unsigned long long)gridDim.x * (unsigned long long)kDenseThreads / L;
+  const unsigned long long g0 = ((unsigned long long)blockIdx.x * (unsigned long long)kDenseThreads + threadIdx.x) / L;
+  const unsigned long long w0 = ((unsigned long long)blockIdx.x * (unsigned long long)kDenseThreads + (threadIdx.x & ~63u)) / L;
+  const uint32_t gl = threadIdx.x & (L - 1u);
+  const unsigned long long inf_bits = 0x7FF0000000000000ull;
+  unsigned long long looked = 0;
+  uint32_t n_found = 0, n_none = 0, n_oor = 0, n_inv = 0;  // (the same in every lane of the wave)
+  double acc[32];
+#pragma unroll
+  for (int i = 0; i < 32; ++i) acc[i] = 0.0;
+  for (unsigned long long it = 0; w0 + it < (unsigned long long)m; it += stride) {
+    const unsigned long long g = g0 + it;
+    int cls = -1;  // past the end
+    double p0 = 0.0, p1 = 0.0, p2 = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    int c0 = 0, c1 = 0, c2 = 0;
+    if (g < (unsigned long long)m) {
+      const float4 pf = pts[g * (unsigned long long)every];  // (g < m: the index is below n)
+      double wp[3];
+      int v[3];
+      cls = probe_classify(pf, a, wp, v);
+      p0 = wp[0], p1 = wp[1], p2 = wp[2];
+      s0 = (double)pf.x, s1 = (double)pf.y, s2 = (double)pf.z;
+      if (cls == 0) c0 = v[0], c1 = v[1], c2 = v[2];
+    }
+    unsigned long long b_bits = inf_bits, b_key = kDenseEmpty;
+    uint32_t b_slot = kDenseDropped;
+    nearest_search<L>(cls, p0, p1, p2, c0, c1, c2, gl, a, tk, reach, max_d2, offs, keys, hits, xyz, b_bits, b_key, b_slot,
+                      looked);
+    int st = -1;
+    if (cls >= 0 && gl == 0) {
+      const bool found = cls == 0 && b_key != kDenseEmpty;
+      st = cls == 1 ? FMX_PROBE_INVALID : cls == 3 ? FMX_PROBE_OUT_OF_RANGE : found ? FMX_PROBE_SOLID : FMX_PROBE_ABSENT;
+      if (found) {
+        const double q[3] = {xyz[3 * (size_t)b_slot + 0], xyz[3 * (size_t)b_slot + 1], xyz[3 * (size_t)b_slot + 2]};
+        const double pj[3] = {s0, s1, s2}, wpj[3] = {p0, p1, p2};
+        double H[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) H[i] = 0.0;
+#pragma unroll
+        for (int r3 = 0; r3 < 3; ++r3) {
+          double r;
+          point_row<1>(a.T.m, a.T.m, q, pj, q, wpj, r3, r, H);  // (X(i) is not read in this mode)
+          accum_row<1>(H, r, inv, acc);
+        }
+      }
+    }
+    n_found += (uint32_t)__popcll(__ballot(st == FMX_PROBE_SOLID));
+    n_none += (uint32_t)__popcll(__ballot(st == FMX_PROBE_ABSENT));
+    n_oor += (uint32_t)__popcll(__ballot(st == FMX_PROBE_OUT_OF_RANGE));
+    n_inv += (uint32_t)__popcll(__ballot(st == FMX_PROBE_INVALID));
+  }
+  const unsigned long long w_looked = wave_sum(looked);
+  if ((threadIdx.x & 63) == 0) {  // results unused: return-less
+    if (n_found) atomicAdd(&cnt[0], (unsigned long long)n_found);
+    if (n_none) atomicAdd(&cnt[1], (unsigned long long)n_none);
+    if (n_oor) atomicAdd(&cnt[2], (unsigned long long)n_oor);
+    if (n_inv) atomicAdd(&cnt[3], (unsigned long long)n_inv);
+    if (w_looked) atomicAdd(&cnt[4], w_looked);
+  }
+  __shared__ double sw[kAlignWaves][NG];
+  __shared__ double sq[kGroups][NG];
+  __shared__ int s_last;
+  const int w = threadIdx.x / kWave, lane = lane_id();
+  const double mine = wave_reduce_scatter32(acc);  // entry lane / 2
+  if ((lane & 1) == 0 && (lane >> 1) < NG) sw[w][lane >> 1] = mine;
+  __syncthreads();
+  if (threadIdx.x < NG) {
+    const int t = threadIdx.x;
+    double bp = sw[0][t];
+#pragma unroll
+    for (int i = 1; i < kAlignWaves; ++i) bp += sw[i][t];
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(bpart + (size_t)blockIdx.x * kAlignLd + t),
+                       (unsigned long long)__double_as_longlong(bp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // every wave's partial stores and counter atomics are acknowledged before its block's ticket
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0)
+    s_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+  __syncthreads();
+  if (!s_last) return;
+  // last block: lane group j (9 of them) sums entry e of blocks j, j + 9, ...; then the group
+  // sums in order
+  const int nblk = gridDim.x;
+  if (threadIdx.x < kGroups * NG) {
+    const int e = threadIdx.x % NG, j = threadIdx.x / NG;
+    double s = 0.0;
+    for (int b = j; b < nblk; b += kGroups)
+      s += __longlong_as_double((long long)__hip_atomic_load(
+          reinterpret_cast<const unsigned long long*>(bpart + (size_t)b * kAlignLd + e), __ATOMIC_RELAXED,
+          __HIP_MEMORY_SCOPE_AGENT));
+    sq[j][e] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < NG) {
+    const int e = threadIdx.x;
+    double s = sq[0][e];
+#pragma unroll
+    for (int j = 1; j < kGroups; ++j) s += sq[j][e];
+    host_store(out + e, s);
+    if (e == NG - 1) host_store(out + NG, 0.5 * s);
+  } else if (threadIdx.x >= 32 && threadIdx.x < 37) {  // (wave 0 too: it publishes what it stored)
+    const int k = threadIdx.x - 32;
+    host_store(reinterpret_cast<unsigned long long*>(out) + kAlignOutCounts + k,
+               __hip_atomic_load(cnt + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  }
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    publish_flag(flag, seq);
   }
 }
 
@@ -1225,6 +1399,33 @@ void run_nearest(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34
   ProfScope ps(c->prof, PROF_DENSE, (double)n * (24.0 + probe_out_bytes(o)), st);
   hipLaunchKernelGGL(k_nearest, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)n, a, probe_take_args(c, f),
                      reach, max_dist2, N.offs.p, D.keys.p, D.tags.p, D.hits.p, D.xyz.p, o, D.probe.cnt.p);
+  FMX_HIP(hipGetLastError());
+}
+
+size_t align_partials() { return (size_t)kNearestBlocks * kAlignLd; }
+
+void run_align(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const double* pose34, const ProbeFilter& f,
+               uint32_t reach, double max_dist2, double sigma, uint32_t seq, hipStream_t st) {
+  auto& D = c->dense;
+  auto& N = D.nearest;
+  auto& A = D.align;
+  if (!N.have) {  // the cube's offsets in shell order, once per context (shared with run_nearest)
+    FMX_HIP(hipMemcpyAsync(N.offs.p, N.h_offs.data(), N.h_offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    N.have = true;
+  }
+  const DenseArgs a = dense_args(c, pose34);
+  const unsigned long long m = ((unsigned long long)n + every - 1) / every;  // the kept points
+  // the grid of run_nearest over the kept points: capped, a grid stride beyond
+  const unsigned long long want = (m * FMX_ALIGN_LANES + kDenseThreads - 1) / kDenseThreads;
+  const uint32_t blocks = (uint32_t)(want < (unsigned long long)kNearestBlocks ? want : (unsigned long long)kNearestBlocks);
+  FMX_HIP(hipMemsetAsync(A.cnt.p, 0, 8 * sizeof(unsigned long long), st));
+  // DESIGN.md §Dense map, Aligning: run_nearest's model without the per-point outputs (the
+  // point, 16, and the own cell's key word, 8; the other lookups are not known at launch), plus
+  // the block partials written and read back (28 doubles each way)
+  ProfScope ps(c->prof, PROF_DENSE, (double)m * 24.0 + (double)blocks * 2.0 * 28.0 * sizeof(double), st);
+  hipLaunchKernelGGL(k_align, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)m, every, a, probe_take_args(c, f),
+                     reach, max_dist2, 1.0 / sigma, N.offs.p, D.keys.p, D.hits.p, D.xyz.p, A.cnt.p, A.bpart.p, A.ticket.p,
+                     A.h_out.d, c->h_flag.d, seq);
   FMX_HIP(hipGetLastError());
 }
 

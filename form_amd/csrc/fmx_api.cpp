@@ -1696,6 +1696,67 @@ void nearest_call(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const
     throw StatusError(FMX_E_STATE, "nearest: a voxel's tag names an integration the context does not know");
 }
 
+// ---- aligning (fmx_align_system, fmx_align_dense; densemap.hip, the align block;
+// align_host.hpp).  align_begin: the checks, the per-call buffers, the scan staged once;
+// align_eval: one system at a pose (one memset, one launch, one wait on the completion word).
+struct AlignCall {
+  const float4* d = nullptr;
+  size_t n = 0;
+  fmx_align_params prm{};
+};
+AlignCall align_begin(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double* pose34,
+                      const fmx_align_params* prm) {
+  auto& D = c->dense;
+  auto& N = D.nearest;
+  auto& A = D.align;
+  if (!D.on) throw StatusError(FMX_E_STATE, "the dense map is not enabled (fmx_dense_configure)");
+  const char* why = "";
+  const fmx_status chk = align_check(xyzw, (unsigned long long)n, pose34, prm, &why);
+  if (chk != FMX_OK) throw StatusError(chk, why);
+  dense_settle(c);
+  AlignCall call;
+  call.n = n;
+  call.prm = *prm;
+  if (!n) return call;
+  // every buffer before anything is launched or written (FMX_E_OOM when one cannot be had)
+  const auto ensure = [](auto& b, size_t m) { roll_ensure(b, m, "dense map align"); };
+  if (!N.have && N.h_offs.empty()) N.h_offs = nearest_offsets(FMX_NEAREST_MAX_REACH);
+  ensure(N.offs, N.h_offs.size());
+  ensure(A.cnt, 8);
+  ensure(A.bpart, align_partials());
+  if (!A.ticket.p) {
+    ensure(A.ticket, 1);
+    FMX_HIP(hipMemsetAsync(A.ticket.p, 0, A.ticket.cap * sizeof(uint32_t), c->stream));
+  }
+  if (!src_on_dev) ensure(D.in, n);
+  A.h_out.ensure(40);
+  call.d = reinterpret_cast<const float4*>(xyzw);
+  if (!src_on_dev) {
+    FMX_HIP(hipMemcpyAsync(D.in.p, xyzw, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    call.d = D.in.p;
+  }
+  return call;
+}
+void align_eval(fmx_ctx* c, const AlignCall& call, const double* pose34, double S[29], fmx_align_counts* cnt) {
+  auto& A = c->dense.align;
+  const uint32_t every = align_stride(call.prm);
+  for (int k = 0; k < 29; ++k) S[k] = 0.0;
+  if (cnt) *cnt = fmx_align_counts{};
+  if (!call.n) return;
+  const uint32_t seq = next_flag(c);
+  run_align(c, call.d, call.n, every, pose34, probe_filter(call.prm.min_hits, call.prm.miss_num, call.prm.miss_den),
+            call.prm.reach, call.prm.max_dist2, call.prm.sigma, seq, c->stream);
+  wait_flag(c, c->h_flag.p, seq);
+  std::memcpy(S, A.h_out.p, 29 * sizeof(double));
+  if (cnt) {
+    unsigned long long k[5];
+    std::memcpy(k, A.h_out.p + 32, sizeof(k));
+    const unsigned long long kept = align_kept((unsigned long long)call.n, every);
+    *cnt = fmx_align_counts{(uint32_t)k[0], (uint32_t)k[1], (uint32_t)k[2], (uint32_t)k[3],
+                            (uint32_t)((unsigned long long)call.n - kept), k[4]};
+  }
+}
+
 // dsk_cells (fmx_register_cloud with deskewing on): the scan's per-cell sweep fractions
 void register_scan(fmx_ctx* c, const float* xyzw, size_t n, int on_dev, fmx_feature_counts* out,
                    const float* dsk_cells = nullptr) {
@@ -3241,6 +3302,38 @@ fmx_status fmx_nearest_voxels(fmx_ctx* c, const float* xyzw, size_t n, int src_o
     unsigned long long k[5];
     nearest_call(c, xyzw, n, src_on_dev, pose34, min_hits, miss_num, miss_den, reach, max_dist2, state, dist2, voxels, k);
     if (counts) *counts = fmx_nearest_counts{(uint32_t)k[0], (uint32_t)k[1], (uint32_t)k[2], (uint32_t)k[3], k[4]};
+  });
+}
+
+// ---- aligning a scan to the dense map (densemap.hip, the align block; align_host.hpp)
+fmx_status fmx_align_system(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double pose34[12],
+                            const fmx_align_params* prm, double out[29], fmx_align_counts* counts) {
+  return guard<false>(c, [&] {
+    if (!c->dense.on) throw StatusError(FMX_E_STATE, "the dense map is not enabled (fmx_dense_configure)");
+    if (!out) throw StatusError(FMX_E_INVAL, "null output");
+    const AlignCall call = align_begin(c, xyzw, n, src_on_dev, pose34, prm);
+    align_eval(c, call, pose34, out, counts);
+  });
+}
+
+fmx_status fmx_align_dense(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double pose_init34[12],
+                           const fmx_align_params* prm, uint32_t max_iters, double threshold, double pose_out34[12],
+                           fmx_align_result* result) {
+  return guard<false>(c, [&] {
+    if (!c->dense.on) throw StatusError(FMX_E_STATE, "the dense map is not enabled (fmx_dense_configure)");
+    const char* why = "";
+    const fmx_status chk = align_loop_check(pose_out34, threshold, &why);
+    if (chk != FMX_OK) throw StatusError(chk, why);
+    const AlignCall call = align_begin(c, xyzw, n, src_on_dev, pose_init34, prm);
+    fmx_align_result R{};
+    double T[12];
+    const fmx_status st = align_loop(
+        pose_init34, max_iters, threshold,
+        [&](const double* pose, double* S, fmx_align_counts* k) { align_eval(c, call, pose, S, k); }, T, &R, &why);
+    if (!R.iters && n && !src_on_dev) stream_wait(c);  // no system waited for the staged scan: the caller owns it again
+    if (st != FMX_OK) throw StatusError(st, why);
+    std::memcpy(pose_out34, T, sizeof(T));
+    if (result) *result = R;
   });
 }
 

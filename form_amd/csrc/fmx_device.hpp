@@ -96,6 +96,24 @@ __device__ __forceinline__ T wave_sum(T v) {
   return v;
 }
 
+// v[0..31] summed over the wave; afterwards lanes 2i and 2i+1 hold entry i in v[0].
+__device__ __forceinline__ double wave_reduce_scatter32(double (&v)[32]) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const int half = 16 >> k;
+    const bool hi = (lane >> (5 - k)) & 1;
+#pragma unroll
+    for (int j = 0; j < half; ++j) {
+      const double a = v[j], b = v[j + half];
+      const double send = hi ? a : b;
+      const double keep = hi ? b : a;
+      v[j] = keep + __shfl_xor(send, 32 >> k, 64);
+    }
+  }
+  return v[0] + __shfl_xor(v[0], 1, 64);
+}
+
 // ---------------------------------------------------------------- host completion word
 // Results the host polls for go to pinned host memory with SYSTEM-scope stores
 // (host_store: sc0 sc1, written through, never left dirty in the GPU L2); the wave

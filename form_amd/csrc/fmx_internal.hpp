@@ -22,6 +22,7 @@
 #include "pair_sort_plan.hpp"
 #include "probe_host.hpp"
 #include "nearest_host.hpp"
+#include "align_host.hpp"
 #include "upload_host.hpp"
 #include "stage.hpp"
 #include "store_plan.hpp"
@@ -670,6 +671,17 @@ struct fmx_ctx {
       std::vector<uint32_t> h_offs;
       fmx::DBuf<uint32_t> offs;
     } nearest;
+    // aligning (fmx_align_system, fmx_align_dense; densemap.hip, the align block): the
+    // counters, k_align's block partials and ticket (0 between launches), and the mapped
+    // host words its last block writes (29 doubles, the counters' bits from word 32).  The
+    // offsets are `nearest`'s, the staged scan is `in`.  Nothing here is allocated, and
+    // nothing launched, unless one of the two entry points is called
+    struct Align {
+      fmx::DBuf<unsigned long long> cnt;
+      fmx::DBuf<double> bpart;
+      fmx::DBuf<uint32_t> ticket;
+      fmx::HBuf<double> h_out;
+    } align;
     // loading voxels back (fmx_upload_voxels; densemap.hip, the upload block): the device copies
     // of a call's entries, grown at first use; nothing below is allocated, and nothing
     // launched, unless that entry point is called
@@ -1067,6 +1079,14 @@ void run_probe_rays(fmx_ctx* c, const float4* d_pts, size_t n, const double* pos
 // allocated c->dense.nearest.offs; its content is sent once (one launch, queued; reads only)
 void run_nearest(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, const ProbeFilter& f, uint32_t reach,
                  double max_dist2, const ProbeOut& o, hipStream_t st);
+// ... aligning: the packed 7 x 7 point-to-point system of the points i % every == 0 against
+// their nearest solid representatives, sigma-whitened, and the class counts, into
+// c->dense.align.h_out behind completion word seq of c->h_flag (one memset and one launch,
+// queued; reads only).  The caller has allocated c->dense.nearest.offs and c->dense.align's
+// buffers (bpart: align_partials() doubles; ticket: one zeroed word) and the completion word
+size_t align_partials();
+void run_align(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const double* pose34, const ProbeFilter& f,
+               uint32_t reach, double max_dist2, double sigma, uint32_t seq, hipStream_t st);
 // ... rolling: {inside, outside} of the box of voxels |v - cc| <= half (one launch, waits for
 // it); then, with c->dense.o_* sized to `evicted` and c->dense.roll.s_* to `kept`, the evicted
 // voxels appended to o_*, the kept ones put back into the emptied table and the device's

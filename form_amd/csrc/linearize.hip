@@ -36,23 +36,7 @@ namespace {
 constexpr int kTotWaves = 16;
 constexpr int kTotLd = 32;  // doubles per block partial (28 used)
 
-// v[0..31] summed over the wave; afterwards lanes 2i and 2i+1 hold entry i in v[0].
-__device__ __forceinline__ double wave_reduce_scatter32(double (&v)[32]) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const int half = 16 >> k;
-    const bool hi = (lane >> (5 - k)) & 1;
-#pragma unroll
-    for (int j = 0; j < half; ++j) {
-      const double a = v[j], b = v[j + half];
-      const double send = hi ? a : b;
-      const double keep = hi ? b : a;
-      v[j] = keep + __shfl_xor(send, 32 >> k, 64);
-    }
-  }
-  return v[0] + __shfl_xor(v[0], 1, 64);
-}
+// (wave_reduce_scatter32: fmx_device.hpp, shared with densemap.hip's k_align)
 
 // Rows in query order (the match outputs, no pair sort): query gq < nq_pl is a plane
 // row (p_i = m_pi, n_i = m_ni, p_j = q_pl), else a point pair (p_i = m_pi, p_j =

@@ -156,6 +156,26 @@ class _NearestCounts(C.Structure):
 
 NEAREST_MAX_REACH = 8  # FMX_NEAREST_MAX_REACH
 
+
+class _AlignParams(C.Structure):
+    _fields_ = [("min_hits", C.c_uint32), ("miss_num", C.c_uint32), ("miss_den", C.c_uint32), ("reach", C.c_uint32),
+                ("max_dist2", C.c_double), ("sigma", C.c_double), ("stride", C.c_uint32)]
+
+
+class _AlignCounts(C.Structure):
+    _fields_ = [("found", C.c_uint32), ("none", C.c_uint32), ("out_of_range", C.c_uint32), ("invalid", C.c_uint32),
+                ("skipped", C.c_uint32), ("lookups", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(found=int(self.found), none=int(self.none), out_of_range=int(self.out_of_range),
+                    invalid=int(self.invalid), skipped=int(self.skipped), lookups=int(self.lookups))
+
+
+class _AlignResult(C.Structure):
+    _fields_ = [("iters", C.c_uint32), ("converged", C.c_int32), ("last_step", C.c_double), ("error", C.c_double),
+                ("counts", _AlignCounts)]
+
+
 # fmx_probe_points / fmx_probe_rays: the per-point state
 PROBE_ABSENT, PROBE_FILTERED, PROBE_SOLID, PROBE_OUT_OF_RANGE, PROBE_INVALID = range(5)
 PROBE_NO_STEP = 0xFFFFFFFF
@@ -223,6 +243,7 @@ EXPORTED = [
     "fmx_probe_points", "fmx_probe_rays",
     "fmx_upload_voxels",
     "fmx_nearest_voxels",
+    "fmx_align_system", "fmx_align_dense",
 ]
 
 PAIR_SORT_FORMS = ("none", "per-block", "tail-scanned", "scatter-scanned")
@@ -986,6 +1007,53 @@ class Context:
         del keep
         return dict(out, state=state, dist2=dist2, counts=cnt.as_dict())
 
+    # ---------------------------------------------------------------- aligning a scan to the map
+    @staticmethod
+    def _align_params(reach, max_dist, sigma, min_hits, max_miss_ratio, stride) -> "_AlignParams":
+        num, den = miss_fraction(max_miss_ratio)
+        md = math.inf if max_dist is None else float(max_dist)
+        return _AlignParams(min_hits, num, den, reach, md * md, float(sigma), stride)
+
+    def align_system(self, points, pose34, reach: int = 1, max_dist=None, sigma: float = 1.0, min_hits: int = 1,
+                     max_miss_ratio=None, stride: int = 1):
+        """fmx_align_system: the point-to-point Gauss-Newton system of the (N, 4) float32 points
+        (numpy, or a torch tensor on the host or the device) at pose34 against their nearest
+        solid representatives (the search of nearest_voxels: reach, max_dist, min_hits,
+        max_miss_ratio), over the points i % stride == 0, whitened by sigma; changes nothing.
+        Returns (system, counts): the packed upper 7 x 7 [H g]^T [H g] and the error, (29,)
+        float64, and the counts found, none, out_of_range, invalid, skipped, lookups."""
+        prm = self._align_params(reach, max_dist, sigma, min_hits, max_miss_ratio, stride)
+        on_dev, ptr, n, keep = _scan_ptr(points)
+        pose = np.ascontiguousarray(pose34, np.float64).reshape(12)
+        if on_dev:
+            _ready(keep)
+        out = np.zeros(29, np.float64)
+        cnt = _AlignCounts()
+        self._chk(self._L.fmx_align_system(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev), _p(pose),
+                                           C.byref(prm), _p(out), C.byref(cnt)))
+        del keep
+        return out, cnt.as_dict()
+
+    def dense_align(self, points, pose_init34, reach: int = 1, max_dist=None, sigma: float = 1.0, min_hits: int = 1,
+                    max_miss_ratio=None, stride: int = 1, max_iters: int = 30, threshold: float = 1e-6) -> dict:
+        """fmx_align_dense: Gauss-Newton on align_system's system from pose_init34 (arguments as
+        align_system), at most max_iters systems, until a step's norm is below threshold;
+        changes nothing.  Returns pose (3, 4), iters, converged, last_step, error and counts
+        (the last system's)."""
+        prm = self._align_params(reach, max_dist, sigma, min_hits, max_miss_ratio, stride)
+        on_dev, ptr, n, keep = _scan_ptr(points)
+        pose = np.ascontiguousarray(pose_init34, np.float64).reshape(12)
+        if on_dev:
+            _ready(keep)
+        out = np.zeros(12, np.float64)
+        res = _AlignResult()
+        self._chk(self._L.fmx_align_dense(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev), _p(pose),
+                                          C.byref(prm), C.c_uint32(max_iters), C.c_double(threshold), _p(out),
+                                          C.byref(res)))
+        del keep
+        return dict(pose=out.reshape(3, 4), iters=int(res.iters), converged=bool(res.converged),
+                    last_step=float(res.last_step), error=float(res.error), counts=res.counts.as_dict())
+
     # ---------------------------------------------------------------- loading voxels back
     def dense_upload(self, points, scan=None, index=None, hits=None, misses=None) -> dict:
         """fmx_upload_voxels: voxel records back into the map, under the keys dense_download,
@@ -1573,6 +1641,29 @@ class FORM:
         found) / n_found) (0.0 when there are none), summed in index order with math.fsum."""
         got = self.dense_nearest(points, radius_m, pose, min_hits, max_miss_ratio)
         return fitness_of(got["state"], got["dist2"])
+
+    def dense_localize(self, points, radius_m: float, pose_guess=None, sigma: float = 0.1, max_iters: int = 30,
+                       threshold: float = 1e-6, stride: int = 1, min_hits: int = 1, max_miss_ratio=None) -> dict:
+        """Register a scan against the dense map (Context.dense_align; points as dense_lookup,
+        pose_guess None: the current pose): point-to-point Gauss-Newton on the nearest solid
+        voxels within radius_m (reach as dense_nearest, ValueError past NEAREST_MAX_REACH).
+        Nothing is changed, the estimator included.  Returns pose (3, 4), iters, converged
+        and, from one more system at that pose, n_valid, n_found, fitness = n_found / n_valid
+        and rmse = sqrt(2 error sigma^2 / n_found) (0.0 where the divisor is 0): dense_fitness's
+        figures over the points i % stride == 0, without a per-point download."""
+        points, T = self._probe_args(points, pose_guess)
+        r = float(radius_m)
+        if not (r >= 0.0) or math.isinf(r):
+            raise ValueError("radius_m must be a finite number >= 0")
+        reach = math.floor(r / float(self._dense["voxel_width"])) + 1
+        if reach > NEAREST_MAX_REACH:
+            raise ValueError(f"radius_m spans more than {NEAREST_MAX_REACH} voxels: reach {reach}")
+        got = self._est.dense_align(points, T, reach, r, sigma, min_hits, max_miss_ratio, stride, max_iters, threshold)
+        S, cnt = self._est.align_system(points, got["pose"], reach, r, sigma, min_hits, max_miss_ratio, stride)
+        n_found, n_valid = cnt["found"], cnt["found"] + cnt["none"]
+        return dict(pose=got["pose"], iters=got["iters"], converged=got["converged"], n_valid=n_valid, n_found=n_found,
+                    fitness=n_found / n_valid if n_valid else 0.0,
+                    rmse=math.sqrt(2.0 * float(S[28]) * float(sigma) * float(sigma) / n_found) if n_found else 0.0)
 
     def _need_dense(self):
         if self._est is None or self._dense is None or not self._dense["enable"]:

@@ -805,6 +805,73 @@ fmx_status fmx_nearest_voxels(fmx_ctx* ctx, const float* xyzw, size_t n_points, 
                               uint32_t reach, double max_dist2, uint8_t* state, double* dist2,
                               const fmx_voxel_arrays* voxels, fmx_nearest_counts* counts);
 
+/* ---------------- aligning a scan to the dense map: registration on the device ---------
+ * Where is the sensor in a map that was built, or loaded back: the point-to-point
+ * Gauss-Newton registration of a scan against the map's solid representatives, the search and
+ * the linearization fused into one launch per iteration that returns 29 doubles and five
+ * counts, nothing per point (DESIGN.md §Dense map, Aligning; tests/align_ref.py restates it).
+ * Both calls only read: the table, the counters, fmx_dense_stats, fmx_dense_last,
+ * fmx_carve_last, the roll state, the spill and the estimator are as before, and
+ * fmx_current_pose is untouched: the alignment does not feed the estimator.
+ *   points   point i with i % stride != 0 (stride 0 reads 1) is skipped: neither classified nor
+ *            searched.  Every other point is classified and searched exactly as
+ *            fmx_nearest_voxels does it (the block above: point, filter, cube, winner), with
+ *            params' min_hits, miss_num, miss_den, reach and max_dist2 in their places there;
+ *   rows     a found point has its sensor-frame point p (the fp32 input widened to double), its
+ *            world point w (the integration's expression) and the winner's representative q,
+ *            and contributes three rows a = 0, 1, 2, R_a being row a of the pose's rotation:
+ *              r_a = w_a - q_a
+ *              H_a = [R_a2 p_1 - R_a1 p_2, R_a0 p_2 - R_a2 p_0, R_a1 p_0 - R_a0 p_1,
+ *                     R_a0, R_a1, R_a2]
+ *            (tangent [w; v], right perturbation: the point-to-point factor of
+ *            fmx_linearize with X(i) the identity and p_i = q);
+ *   output   with inv = 1 / sigma and v = [H_a * inv, -r_a * inv], out[0..27] is the packed
+ *            upper 7 x 7 of the sum of v v^T over all rows, packed as fmx_linearize_matched
+ *            packs it (index r * 7 - r (r - 1) / 2 + (q - r)), and out[28] = 0.5 * the sum of
+ *            (r_a * inv)^2.  Per-point terms are fp64 without contraction;
+ *   order    the order of the sum is the kernel's, fixed by n_points, stride and the launch
+ *            grid alone and not by the order the threads run in: two calls with the same
+ *            arguments on the same map return the same 29 bit patterns, from a host and from
+ *            a device pointer alike.  The class counts are the definition's exactly;
+ *            counts->lookups is fmx_nearest_counts' diagnostic, under its bounds.
+ * fmx_align_dense is fmx_register_points' loop on that system.  From T = pose_init, while
+ * iters < max_iters: evaluate the system at T (++iters), solve H dx = g by Cholesky, T = T *
+ * Exp(dx), stop once ||dx|| < threshold.  The scan is staged to the device once per call; an
+ * iteration is one memset of the counters, one launch, one wait on a completion word and the
+ * host's 6 x 6 solve.  max_iters == 0 returns pose_init with iters = 0.
+ * Status codes: FMX_E_STATE unless the dense map is configured and enabled, and, pose_out left
+ * unwritten, when a system is singular (too few found points); FMX_E_INVAL for NULL params,
+ * out, pose or pose_out, a non-finite pose, NULL points with n_points > 0, n_points >= 2^32,
+ * reach > FMX_NEAREST_MAX_REACH, a NaN or negative max_dist2, a sigma that is not finite and
+ * positive, a NaN or negative threshold; FMX_E_OOM, nothing written, when a per-call buffer
+ * cannot be allocated.  fmx_align_system with n_points == 0 succeeds with an all-zero system
+ * and launches nothing.  A context that calls neither allocates and launches nothing for
+ * them. */
+typedef struct fmx_align_params {
+  uint32_t min_hits, miss_num, miss_den;  /* fmx_carve_download's filter */
+  uint32_t reach;                         /* <= FMX_NEAREST_MAX_REACH */
+  double max_dist2;                       /* fmx_nearest_voxels' rule */
+  double sigma;                           /* > 0, finite */
+  uint32_t stride;                        /* use points with i % stride == 0; 0 = 1 */
+} fmx_align_params;
+typedef struct fmx_align_counts {
+  uint32_t found, none, out_of_range, invalid, skipped;  /* the five sum to n */
+  uint64_t lookups;                                      /* diagnostic, as fmx_nearest_counts */
+} fmx_align_counts;
+fmx_status fmx_align_system(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                            const double pose34[12], const fmx_align_params* params, double out[29],
+                            fmx_align_counts* counts /* may be NULL */);
+typedef struct fmx_align_result {
+  uint32_t iters;          /* systems evaluated */
+  int32_t converged;       /* 1 iff the last step's norm < threshold */
+  double last_step;        /* ||dx|| of the last step, 0 when iters == 0 */
+  double error;            /* out[28] of the last system evaluated */
+  fmx_align_counts counts; /* of the last system evaluated */
+} fmx_align_result;
+fmx_status fmx_align_dense(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                           const double pose_init34[12], const fmx_align_params* params, uint32_t max_iters,
+                           double threshold, double pose_out34[12], fmx_align_result* result /* may be NULL */);
+
 /* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
  * pose at the middle of the last registered sweep. */
 fmx_status fmx_current_pose(fmx_ctx* ctx, double pose34[12]);
