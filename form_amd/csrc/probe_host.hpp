@@ -1,7 +1,9 @@
 // probe_host.hpp — the host-only parts of probing the dense map (include/fmx/fmx.h,
-// fmx_probe_points; densemap.hip, the probe block): the argument checks, the ray origin's
-// range rule and the tag -> scan_idx resolution of the per-point results.  No device code and
-// no HIP header: tests/cpp/test_probe_host.cpp builds it alone, under the host sanitizers.
+// fmx_probe_points; densemap.hip, the probe block; called from dense_api.cpp): the argument
+// checks (the scan-and-pose part of them also fmx_dense_integrate's and fmx_carve_rays'), the
+// ray origin's range rule and the tag -> scan_idx resolution of the per-point results.  No
+// device code and no HIP header: tests/cpp/test_probe_host.cpp builds it alone, under the
+// host sanitizers.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -14,9 +16,11 @@
 
 namespace fmx {
 
-// FMX_OK, or FMX_E_INVAL and *why: a NULL or non-finite pose, 2^32 points or more, NULL
-// points with n > 0.
-inline fmx_status probe_check(const void* points, unsigned long long n, const double* pose34, const char** why) {
+// The checks every call that takes a scan and a pose makes, in this order.  FMX_OK, or
+// FMX_E_INVAL and *why: a NULL or non-finite pose, 2^32 points or more (too_many: the call's
+// own text for that), NULL points with n > 0.
+inline fmx_status scan_check(const void* points, unsigned long long n, const double* pose34, const char* too_many,
+                             const char** why) {
   if (!pose34) {
     *why = "null pose";
     return FMX_E_INVAL;
@@ -27,7 +31,7 @@ inline fmx_status probe_check(const void* points, unsigned long long n, const do
       return FMX_E_INVAL;
     }
   if (n >= (1ull << 32)) {
-    *why = "a probe holds fewer than 2^32 points";
+    *why = too_many;
     return FMX_E_INVAL;
   }
   if (n && !points) {
@@ -35,6 +39,10 @@ inline fmx_status probe_check(const void* points, unsigned long long n, const do
     return FMX_E_INVAL;
   }
   return FMX_OK;
+}
+// The probes' (and, through nearest_check and align_check, the search's and the alignment's).
+inline fmx_status probe_check(const void* points, unsigned long long n, const double* pose34, const char** why) {
+  return scan_check(points, n, pose34, "a probe holds fewer than 2^32 points", why);
 }
 
 // A ray cast starts in the voxel of the pose's translation: the carve's rule, unchanged.
