@@ -63,13 +63,14 @@ inline void align_unpack(const double S[29], double H[6][6], double g[6]) {
 
 // fmx_register_points' loop.  system_at(pose34, S, counts) evaluates the packed system at a
 // pose.  FMX_OK with pose_out and *res (may be NULL) written, or FMX_E_STATE with neither
-// touched when a system is singular.
-template <class SystemAt>
-fmx_status align_loop(const double pose_init[12], uint32_t max_iters, double threshold, SystemAt&& system_at,
-                      double pose_out[12], fmx_align_result* res, const char** why) {
+// touched when a system is singular.  Result: fmx_align_result, or fmx_plane_result for the
+// point-to-plane system (the same fields over another set of counts).
+template <class Result, class SystemAt>
+fmx_status align_loop_as(const double pose_init[12], uint32_t max_iters, double threshold, SystemAt&& system_at,
+                         double pose_out[12], Result* res, const char** why) {
   fmxh::Pose T;
   std::memcpy(T.m, pose_init, sizeof(T.m));
-  fmx_align_result R{};
+  Result R{};
   while (R.iters < max_iters) {
     double S[29];
     system_at(T.m, S, &R.counts);
@@ -91,6 +92,11 @@ fmx_status align_loop(const double pose_init[12], uint32_t max_iters, double thr
   std::memcpy(pose_out, T.m, sizeof(T.m));
   if (res) *res = R;
   return FMX_OK;
+}
+template <class SystemAt>
+fmx_status align_loop(const double pose_init[12], uint32_t max_iters, double threshold, SystemAt&& system_at,
+                      double pose_out[12], fmx_align_result* res, const char** why) {
+  return align_loop_as<fmx_align_result>(pose_init, max_iters, threshold, system_at, pose_out, res, why);
 }
 
 }  // namespace fmx

@@ -1,6 +1,6 @@
 // dense_api.cpp — the host layer of the dense voxel map (densemap.hip): every fmx_dense_*,
-// fmx_roll_*, fmx_carve_*, fmx_probe_*, fmx_upload_*, fmx_nearest_* and fmx_align_* entry
-// point of include/fmx/fmx.h, and the four calls register_scan (fmx_api.cpp) makes into the
+// fmx_roll_*, fmx_carve_*, fmx_probe_*, fmx_upload_*, fmx_nearest_*, fmx_align_*, fmx_normals_*
+// and fmx_plane_* entry point of include/fmx/fmx.h, and the four calls register_scan (fmx_api.cpp) makes into the
 // map (fmx_api.hpp).  The argument checks that need no device live in the *_host.hpp headers.
 // Host code only; built like fmx_api.cpp.
 #include <algorithm>
@@ -19,6 +19,9 @@ namespace {
 void need_map(const fmx_ctx* c) {
   if (!c->dense.on) throw StatusError(FMX_E_STATE, "the dense map is not enabled (fmx_dense_configure)");
 }
+// The normal snapshot is indexed by slot and depends on hits and misses: every path that
+// changes, or may change, the table ends it here (one host-side flag: nothing is launched).
+void normals_stale(fmx_ctx* c) { c->dense.normals.current = false; }
 // A host-only check (the *_host.hpp ones return a status and write a text): its refusal thrown.
 template <class F>
 void checked(F&& check) {
@@ -87,6 +90,10 @@ void dense_release(fmx_ctx* c) {
   D.carve.cfg = CarveCfg{};
   D.carve.last = fmx_carve_counts{};
   D.carve.last_carved = 0;
+  D.normals.nrm.release();  // (the snapshot belongs to the table it was built from)
+  D.normals.support.release();
+  D.normals.built = D.normals.current = false;
+  D.normals.voxels = D.normals.oriented = D.normals.solid = 0;
   D.max_voxels = D.slots = D.voxels = 0;
   D.seq_scan.clear();
   D.integrations = 0;
@@ -96,6 +103,7 @@ void dense_release(fmx_ctx* c) {
 // behind what the context stream holds; carve_finish waits for them.
 void carve_queue(fmx_ctx* c, const float4* d, size_t n, const double* pose34, uint32_t mark) {
   auto& Cv = c->dense.carve;
+  normals_stale(c);
   run_carve(c, d, n, pose34, mark, Cv.flag_seq + 1, c->stream);
   Cv.flag_seq = Cv.pending = Cv.flag_seq + 1;
 }
@@ -169,6 +177,7 @@ void roll_rebuild(fmx_ctx* c, const long long cc[3], const uint32_t half[3], uin
     roll_ensure(D.carve.o_miss, evicted);
     if (kept) roll_ensure(D.carve.s_miss, kept);
   }
+  normals_stale(c);
   run_roll_rebuild(c, cc, half, kept, evicted, c->stream);
   D.voxels = kept;
 }
@@ -266,24 +275,40 @@ AlignCall align_begin(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, c
   call.d = scan_on_device(c, xyzw, n, src_on_dev);
   return call;
 }
-void align_eval(fmx_ctx* c, const AlignCall& call, const double* pose34, double S[29], fmx_align_counts* cnt) {
+// run: run_align or run_plane.  S and the kernel's counters k (the point rows write five of
+// the six), all zero when there are no points.
+void align_launch(fmx_ctx* c, const AlignCall& call, const double* pose34, decltype(run_align)* run, double S[29],
+                  unsigned long long k[6]) {
   auto& A = c->dense.align;
-  const uint32_t every = align_stride(call.prm);
-  for (int k = 0; k < 29; ++k) S[k] = 0.0;
-  if (cnt) *cnt = fmx_align_counts{};
+  for (int i = 0; i < 29; ++i) S[i] = 0.0;
+  for (int i = 0; i < 6; ++i) k[i] = 0;
   if (!call.n) return;
   const uint32_t seq = next_flag(c);
-  run_align(c, call.d, call.n, every, pose34, probe_filter(call.prm.min_hits, call.prm.miss_num, call.prm.miss_den),
-            call.prm.reach, call.prm.max_dist2, call.prm.sigma, seq, c->stream);
+  run(c, call.d, call.n, align_stride(call.prm), pose34, probe_filter(call.prm.min_hits, call.prm.miss_num, call.prm.miss_den),
+      call.prm.reach, call.prm.max_dist2, call.prm.sigma, seq, c->stream);
   wait_flag(c, c->h_flag.p, seq);
   std::memcpy(S, A.h_out.p, 29 * sizeof(double));
-  if (cnt) {
-    unsigned long long k[5];
-    std::memcpy(k, A.h_out.p + 32, sizeof(k));
-    const unsigned long long kept = align_kept((unsigned long long)call.n, every);
+  std::memcpy(k, A.h_out.p + 32, (run == run_plane ? 6 : 5) * sizeof(unsigned long long));
+}
+void align_eval(fmx_ctx* c, const AlignCall& call, const double* pose34, double S[29], fmx_align_counts* cnt) {
+  unsigned long long k[6];
+  align_launch(c, call, pose34, run_align, S, k);
+  const unsigned long long kept = align_kept((unsigned long long)call.n, align_stride(call.prm));
+  if (cnt)
     *cnt = fmx_align_counts{(uint32_t)k[0], (uint32_t)k[1], (uint32_t)k[2], (uint32_t)k[3],
                             (uint32_t)((unsigned long long)call.n - kept), k[4]};
-  }
+}
+void plane_eval(fmx_ctx* c, const AlignCall& call, const double* pose34, double S[29], fmx_plane_counts* cnt) {
+  unsigned long long k[6];
+  align_launch(c, call, pose34, run_plane, S, k);
+  if (cnt) *cnt = plane_counts(k, (unsigned long long)call.n, align_stride(call.prm));
+}
+// fmx_plane_*: the map on and the normal snapshot current.
+void need_normals(const fmx_ctx* c) {
+  need_map(c);
+  if (!c->dense.normals.current)
+    throw StatusError(FMX_E_STATE, c->dense.normals.built ? "the normal snapshot is stale: the table changed since fmx_normals_build"
+                                                          : "no normal snapshot (fmx_normals_build)");
 }
 
 }  // namespace
@@ -309,6 +334,7 @@ uint32_t dense_queue(fmx_ctx* c, const float4* d, size_t n, const double* pose34
   Cv.last_carved = Cv.have && Cv.cfg.on && D.integrations % Cv.cfg.every == 0 ? 1 : 0;
   if (n) {
     flag = D.flag_seq + 1;
+    normals_stale(c);
     run_dense_integrate(c, d, n, pose34, seq, flag, c->stream);
     D.flag_seq = D.pending = flag;
     if (Cv.last_carved && carve_origin_ok(pose34, D.voxel_w)) carve_queue(c, d, n, pose34, seq + 1);
@@ -558,6 +584,7 @@ fmx_status fmx_upload_voxels(fmx_ctx* c, const fmx_voxel_input* in, uint32_t n, 
     // (within the reserved room; before the launches, so that no tag ever names an owner the table lacks)
     D.seq_scan.insert(D.seq_scan.end(), own.scans.begin(), own.scans.end());
     D.used = true;  // the configuration is final, as after an integration
+    normals_stale(c);
     run_dense_upload(c, n, in->index != nullptr, in->hits != nullptr, in->misses != nullptr, own.temp, c->stream);
     FMX_HIP(hipMemcpyAsync(U.h_cnt.p, U.cnt.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns the arrays again (own.owner too)
@@ -572,6 +599,7 @@ fmx_status fmx_dense_clear(fmx_ctx* c) {
     auto& D = c->dense;
     need_map(c);
     dense_settle(c);
+    normals_stale(c);
     run_dense_clear(c, c->stream);
     D.voxels = 0;
     D.seq_scan.clear();
@@ -806,6 +834,124 @@ fmx_status fmx_align_dense(fmx_ctx* c, const float* xyzw, size_t n, int src_on_d
     const fmx_status st = align_loop(
         pose_init34, max_iters, threshold,
         [&](const double* pose, double* S, fmx_align_counts* k) { align_eval(c, call, pose, S, k); }, T, &R, &why);
+    if (!R.iters && n && !src_on_dev) stream_wait(c);  // no system waited for the staged scan: the caller owns it again
+    if (st != FMX_OK) throw StatusError(st, why);
+    std::memcpy(pose_out34, T, sizeof(T));
+    if (result) *result = R;
+  });
+}
+
+// ---- surface normals of the dense map (normals_host.hpp)
+fmx_status fmx_normals_build(fmx_ctx* c, const fmx_normals_params* prm, fmx_normals_counts* counts) {
+  return guard<false>(c, [&] {
+    auto& D = c->dense;
+    auto& M = D.normals;
+    need_map(c);
+    checked([&](const char** why) { return normals_check(prm, why); });
+    dense_settle(c);
+    // every buffer before anything is launched or changed (FMX_E_OOM when one cannot be had)
+    offsets_ensure(c, "dense map normals");
+    roll_ensure(M.cnt, 8, "dense map normals");
+    if (!M.nrm.p || !M.support.p) {  // exactly `slots` entries each, as the table's own arrays
+      DBuf<float4> nrm;
+      DBuf<uint32_t> support;
+      alloc_exact(nrm, D.slots);
+      alloc_exact(support, D.slots);
+      M.nrm = std::move(nrm);
+      M.support = std::move(support);
+    }
+    try {
+      M.h_cnt.ensure(8);
+    } catch (const HipError&) {
+      (void)hipGetLastError();
+      throw StatusError(FMX_E_OOM, "dense map normals: pinned host allocation failed");
+    }
+    fmx_normals_counts out{};
+    if (D.voxels) {  // (an empty table: nothing to launch, no record is ever indexed)
+      M.current = false;
+      run_normals_build(c, *prm, c->stream);
+      FMX_HIP(hipMemcpyAsync(M.h_cnt.p, M.cnt.p, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+      FMX_HIP(hipStreamSynchronize(c->stream));
+      const unsigned long long* k = M.h_cnt.p;
+      out = fmx_normals_counts{(uint32_t)k[0], (uint32_t)k[1], (uint32_t)k[2], (uint32_t)k[3], k[4]};
+    }
+    M.prm = *prm;
+    M.voxels = D.voxels;
+    M.oriented = out.oriented;
+    M.solid = normals_take(out, false);
+    M.built = M.current = true;
+    if (counts) *counts = out;
+  });
+}
+
+fmx_status fmx_normals_stats(fmx_ctx* c, uint64_t out[4]) {
+  return guard<false>(c, [&] {
+    if (!out) throw StatusError(FMX_E_INVAL, "null output");
+    const auto& M = c->dense.normals;
+    out[0] = M.built ? 1 : 0;
+    out[1] = M.current ? 1 : 0;
+    out[2] = M.voxels;
+    out[3] = M.oriented;
+  });
+}
+
+fmx_status fmx_normals_download(fmx_ctx* c, int oriented_only, const fmx_voxel_arrays* arrays, float* normal,
+                                float* flatness, uint32_t* support, uint32_t* n) {
+  return guard<false>(c, [&] {
+    auto& D = c->dense;
+    auto& M = D.normals;
+    need_normals(c);
+    dense_settle(c);
+    if (!n) throw StatusError(FMX_E_INVAL, "null count");
+    const fmx_voxel_arrays A = arrays ? *arrays : fmx_voxel_arrays{};
+    const uint32_t count = (uint32_t)(oriented_only ? M.oriented : M.solid);
+    if (!any_array(A) && !normal && !flatness && !support) {  // the sizing call
+      *n = count;
+      return;
+    }
+    if (*n < count)
+      throw StatusError(FMX_E_SIZE, "dense map normals download: room for " + std::to_string(*n) + " of " +
+                                        std::to_string(count) + " voxels");
+    if (count) {
+      const bool with_misses = A.misses && D.carve.have;
+      if (with_misses) D.carve.o_miss.ensure(count);
+      run_normals_compact(c, M.prm, oriented_only != 0, with_misses, count, c->stream);
+      const auto out = [&](void* dst, const void* src, size_t bytes) {
+        if (dst) FMX_HIP(hipMemcpyAsync(dst, src, count * bytes, hipMemcpyDeviceToHost, c->stream));
+      };
+      out(normal, M.o_normal.p, 3 * sizeof(float));
+      out(flatness, M.o_flat.p, sizeof(float));
+      out(support, M.o_support.p, sizeof(uint32_t));
+      list_fetch(c, count, A);  // (waits)
+    }
+    *n = count;
+  });
+}
+
+// ---- point-to-plane alignment against the normals (align_host.hpp's checks and loop)
+fmx_status fmx_plane_system(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double pose34[12],
+                            const fmx_align_params* prm, double out[29], fmx_plane_counts* counts) {
+  return guard<false>(c, [&] {
+    need_normals(c);
+    if (!out) throw StatusError(FMX_E_INVAL, "null output");
+    const AlignCall call = align_begin(c, xyzw, n, src_on_dev, pose34, prm);
+    plane_eval(c, call, pose34, out, counts);
+  });
+}
+
+fmx_status fmx_plane_align(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double pose_init34[12],
+                           const fmx_align_params* prm, uint32_t max_iters, double threshold, double pose_out34[12],
+                           fmx_plane_result* result) {
+  return guard<false>(c, [&] {
+    need_normals(c);
+    checked([&](const char** why) { return align_loop_check(pose_out34, threshold, why); });
+    const AlignCall call = align_begin(c, xyzw, n, src_on_dev, pose_init34, prm);
+    fmx_plane_result R{};
+    double T[12];
+    const char* why = "";
+    const fmx_status st = align_loop_as<fmx_plane_result>(
+        pose_init34, max_iters, threshold,
+        [&](const double* pose, double* S, fmx_plane_counts* k) { plane_eval(c, call, pose, S, k); }, T, &R, &why);
     if (!R.iters && n && !src_on_dev) stream_wait(c);  // no system waited for the staged scan: the caller owns it again
     if (st != FMX_OK) throw StatusError(st, why);
     std::memcpy(pose_out34, T, sizeof(T));

@@ -2,8 +2,9 @@
 // include/fmx/fmx.h, fmx_dense_integrate).  A fixed-capacity open-addressed hash of world
 // voxels, structure-of-arrays, 44 B per slot: keys (u64), tags (u64), hits (u32), xyz
 // (3 doubles); 52 B once carving has been enabled (misses and seen, u32 each: the carve
-// block further down; the probe block behind it only reads the table; the upload block behind
-// that puts downloaded voxels back).  An integration is
+// block further down; the probe, nearest, align and normals blocks behind it only read the
+// table, the normals into 20 B per slot of their own; the upload block behind those puts
+// downloaded voxels back).  An integration is
 // two launches on one stream, no host round trip between them; the kernel boundary is the
 // only ordering (no in-kernel device-scope fence: see organize.hip's header for what one per
 // wave costs on gfx950).
@@ -847,6 +848,44 @@ static_assert(FMX_NEAREST_AHEAD >= 1, "FMX_NEAREST_AHEAD is at least 1");
 #endif
 constexpr int kNearestBlocks = FMX_NEAREST_BLOCKS;  // the grid's cap: a grid stride beyond it
 
+// The walk over a range of the cube: the cells [lo, hi) of the offset list around the cell c,
+// every L-th of them from lo + gl, with the look-ahead described above; each present voxel that
+// is solid under tk goes to visit(key, slot).  `looked` grows by the cells looked up.  Shared by
+// nearest_search (a shell per call) and k_normals_build (the whole cube in one).
+template <uint32_t L, class Visit>
+__device__ __forceinline__ void cube_visit(uint32_t lo, uint32_t hi, uint32_t gl, int c0, int c1, int c2, uint32_t slot_mask,
+                                           const DenseTake& tk, const uint32_t* __restrict__ offs,
+                                           const unsigned long long* __restrict__ keys,
+                                           const uint32_t* __restrict__ hits, unsigned long long& looked, Visit&& visit) {
+  constexpr int kLimit = (1 << 20) - 1;
+  for (uint32_t base = lo + gl; base < hi; base += L * (uint32_t)FMX_NEAREST_AHEAD) {
+    unsigned long long key[FMX_NEAREST_AHEAD], k0[FMX_NEAREST_AHEAD];
+    uint32_t h0[FMX_NEAREST_AHEAD];
+    bool ok[FMX_NEAREST_AHEAD];
+#pragma unroll
+    for (int u = 0; u < FMX_NEAREST_AHEAD; ++u) {
+      const uint32_t at = base + (uint32_t)u * L;
+      // (at < hi <= (2 reach + 1)^3, the list's length: the host checked the reach)
+      const uint32_t od = at < hi ? offs[at] : 0u;
+      const int x = c0 + (int)(od & 255u) - FMX_NEAREST_MAX_REACH, y = c1 + (int)((od >> 8) & 255u) - FMX_NEAREST_MAX_REACH,
+                z = c2 + (int)((od >> 16) & 255u) - FMX_NEAREST_MAX_REACH;
+      // a cell that cannot be stored is skipped (each coordinate + bias is then a 21-bit field)
+      ok[u] = at < hi && abs(x) < kLimit && abs(y) < kLimit && abs(z) < kLimit;
+      key[u] = dense_key(x, y, z);
+      h0[u] = (uint32_t)mix64(key[u]) & slot_mask;
+      k0[u] = ok[u] ? keys[h0[u]] : kDenseEmpty;
+      looked += ok[u] ? 1ull : 0ull;
+    }
+#pragma unroll
+    for (int u = 0; u < FMX_NEAREST_AHEAD; ++u) {
+      if (ok[u]) {
+        const uint32_t slot = probe_find(key[u], h0[u], k0[u], keys, slot_mask);
+        if (slot != kDenseDropped && dense_take(tk, hits[slot], slot)) visit(key[u], slot);
+      }
+    }
+  }
+}
+
 // One point group's search, the per-trip body shared by k_nearest and k_align: the shell loop,
 // the look-ahead loads, the group butterfly and the early stop, as described above.  cls: the
 // point's class (0: in range, p its world point and c its own voxel; anything else: no point
@@ -862,48 +901,23 @@ __device__ __forceinline__ void nearest_search(int cls, double p0, double p1, do
                                                const uint32_t* __restrict__ hits, const double* __restrict__ xyz,
                                                unsigned long long& b_bits, unsigned long long& b_key, uint32_t& b_slot,
                                                unsigned long long& looked) {
-  constexpr int kLimit = (1 << 20) - 1;
   bool done = cls != 0;
   for (uint32_t s = 0; s <= reach; ++s) {
     if (!__any(!done)) break;  // (the whole wave)
     if (!done) {
       const uint32_t lo = s ? (2u * s - 1u) * (2u * s - 1u) * (2u * s - 1u) : 0u, hi = (2u * s + 1u) * (2u * s + 1u) * (2u * s + 1u);
-      for (uint32_t base = lo + gl; base < hi; base += L * (uint32_t)FMX_NEAREST_AHEAD) {
-        unsigned long long key[FMX_NEAREST_AHEAD], k0[FMX_NEAREST_AHEAD];
-        uint32_t h0[FMX_NEAREST_AHEAD];
-        bool ok[FMX_NEAREST_AHEAD];
-#pragma unroll
-        for (int u = 0; u < FMX_NEAREST_AHEAD; ++u) {
-          const uint32_t at = base + (uint32_t)u * L;
-          // (at < hi <= (2 reach + 1)^3, the list's length: the host checked the reach)
-          const uint32_t od = at < hi ? offs[at] : 0u;
-          const int x = c0 + (int)(od & 255u) - FMX_NEAREST_MAX_REACH, y = c1 + (int)((od >> 8) & 255u) - FMX_NEAREST_MAX_REACH,
-                    z = c2 + (int)((od >> 16) & 255u) - FMX_NEAREST_MAX_REACH;
-          // a cell that cannot be stored is skipped (each coordinate + bias is then a 21-bit field)
-          ok[u] = at < hi && abs(x) < kLimit && abs(y) < kLimit && abs(z) < kLimit;
-          key[u] = dense_key(x, y, z);
-          h0[u] = (uint32_t)mix64(key[u]) & a.slot_mask;
-          k0[u] = ok[u] ? keys[h0[u]] : kDenseEmpty;
-          looked += ok[u] ? 1ull : 0ull;
-        }
-#pragma unroll
-        for (int u = 0; u < FMX_NEAREST_AHEAD; ++u) {
-          if (ok[u]) {
-            const uint32_t slot = probe_find(key[u], h0[u], k0[u], keys, a.slot_mask);
-            if (slot != kDenseDropped && dense_take(tk, hits[slot], slot)) {
-              const double e0 = xyz[3 * (size_t)slot + 0] - p0, e1 = xyz[3 * (size_t)slot + 1] - p1,
-                           e2 = xyz[3 * (size_t)slot + 2] - p2;
-              const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
-              const unsigned long long bits = (unsigned long long)__double_as_longlong(d2);
-              if (d2 <= max_d2 && (bits < b_bits || (bits == b_bits && key[u] < b_key))) {
-                b_bits = bits;
-                b_key = key[u];
-                b_slot = slot;
-              }
-            }
-          }
-        }
-      }
+      cube_visit<L>(lo, hi, gl, c0, c1, c2, a.slot_mask, tk, offs, keys, hits, looked,
+                    [&](unsigned long long key, uint32_t slot) {
+                      const double e0 = xyz[3 * (size_t)slot + 0] - p0, e1 = xyz[3 * (size_t)slot + 1] - p1,
+                                   e2 = xyz[3 * (size_t)slot + 2] - p2;
+                      const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+                      const unsigned long long bits = (unsigned long long)__double_as_longlong(d2);
+                      if (d2 <= max_d2 && (bits < b_bits || (bits == b_bits && key < b_key))) {
+                        b_bits = bits;
+                        b_key = key;
+                        b_slot = slot;
+                      }
+                    });
     }
     if (s == 0 && reach != 0) continue;  // (uniform: the own cell alone certifies nothing)
     // the group's best in every lane of it (a done group repeats its own: harmless)
@@ -1012,14 +1026,31 @@ static_assert(FMX_ALIGN_LANES >= 1 && FMX_ALIGN_LANES <= 64 && (FMX_ALIGN_LANES 
               "FMX_ALIGN_LANES is a power of two from 1 to 64");
 constexpr int kAlignWaves = kDenseThreads / kWave;
 constexpr int kAlignLd = 32;  // doubles per block partial (28 used)
-constexpr int kAlignOutCounts = 32;  // out[32..36]: the counters' bit patterns behind the 29 doubles
+constexpr int kAlignOutCounts = 32;  // out[32..36] (..37: PlaneRows): the counters' bit patterns behind the 29 doubles
 
 namespace {
 #include "factor_rows.hpp"
 }  // namespace
 
-// m: the kept points, ceil(n / every).  cnt: {found, none, out_of_range, invalid, lookups},
-// zeroed by the caller.  ticket: 0 at launch, 0 again afterwards.  out: mapped host memory.
+//
+// The row kind is the kernel's template parameter.  PointRows: the three point-to-point rows
+// above.  PlaneRows (DESIGN.md §Dense map, Plane alignment; fmx_plane_system): the winner's
+// slot also names its record of the normal snapshot (16 B more per found point); a winner
+// without a normal makes the point *unoriented* (a sixth counter, nothing added), any other
+// adds the one row of plane_row<1> (X(i) the identity, p_i = q, n_i = n) into the same 28 sums.
+struct PointRows {
+  static constexpr int kCounters = 5;
+};
+struct PlaneRows {
+  static constexpr int kCounters = 6;
+  const float4* __restrict__ nrm;  // per slot: {n0, n1, n2, flatness}, all-zero n unless oriented
+};
+constexpr int kAlignUnoriented = 5;  // a point's class beside FMX_PROBE_* (0 .. 4): found, winner without a normal
+
+// m: the kept points, ceil(n / every).  cnt: {found, none, out_of_range, invalid, lookups,
+// unoriented (PlaneRows)}, zeroed by the caller.  ticket: 0 at launch, 0 again afterwards.  out:
+// mapped host memory.
+template <class Rows>
 __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restrict__ pts, uint32_t m, uint32_t every,
                                                          DenseArgs a, DenseTake tk, uint32_t reach, double max_d2,
                                                          double inv, const uint32_t* __restrict__ offs,
@@ -1028,7 +1059,8 @@ __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restric
                                                          const double* __restrict__ xyz,
                                                          unsigned long long* __restrict__ cnt, double* __restrict__ bpart,
                                                          uint32_t* __restrict__ ticket, double* __restrict__ out,
-                                                         uint32_t* __restrict__ flag, uint32_t seq) {
+                                                         uint32_t* __restrict__ flag, uint32_t seq, Rows rows) {
+  constexpr bool kPlane = Rows::kCounters == 6;
   constexpr uint32_t L = (uint32_t)FMX_ALIGN_LANES;
   constexpr int NG = 28;
   constexpr int kGroups = kDenseThreads / NG;  // final reduction: lane groups x 28 entries
@@ -1039,6 +1071,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restric
   const unsigned long long inf_bits = 0x7FF0000000000000ull;
   unsigned long long looked = 0;
   uint32_t n_found = 0, n_none = 0, n_oor = 0, n_inv = 0;  // (the same in every lane of the wave)
+  [[maybe_unused]] uint32_t n_unor = 0;
   double acc[32];
 #pragma unroll
   for (int i = 0; i < 32; ++i) acc[i] = 0.0;
@@ -1070,14 +1103,28 @@ __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restric
         double H[12];
 #pragma unroll
         for (int i = 0; i < 12; ++i) H[i] = 0.0;
+        if constexpr (kPlane) {
+          const float4 nf = rows.nrm[b_slot];
+          if (nf.x == 0.0f && nf.y == 0.0f && nf.z == 0.0f) {
+            st = kAlignUnoriented;
+          } else {
+            const double ni[3] = {(double)nf.x, (double)nf.y, (double)nf.z};
+            const double eye[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};  // X(i)
+            double r;
+            plane_row<1>(eye, a.T.m, q, ni, pj, r, H);
+            accum_row<1>(H, r, inv, acc);
+          }
+        } else {
 #pragma unroll
-        for (int r3 = 0; r3 < 3; ++r3) {
-          double r;
-          point_row<1>(a.T.m, a.T.m, q, pj, q, wpj, r3, r, H);  // (X(i) is not read in this mode)
-          accum_row<1>(H, r, inv, acc);
+          for (int r3 = 0; r3 < 3; ++r3) {
+            double r;
+            point_row<1>(a.T.m, a.T.m, q, pj, q, wpj, r3, r, H);  // (X(i) is not read in this mode)
+            accum_row<1>(H, r, inv, acc);
+          }
         }
       }
     }
+    if constexpr (kPlane) n_unor += (uint32_t)__popcll(__ballot(st == kAlignUnoriented));
     n_found += (uint32_t)__popcll(__ballot(st == FMX_PROBE_SOLID));
     n_none += (uint32_t)__popcll(__ballot(st == FMX_PROBE_ABSENT));
     n_oor += (uint32_t)__popcll(__ballot(st == FMX_PROBE_OUT_OF_RANGE));
@@ -1090,6 +1137,8 @@ __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restric
     if (n_oor) atomicAdd(&cnt[2], (unsigned long long)n_oor);
     if (n_inv) atomicAdd(&cnt[3], (unsigned long long)n_inv);
     if (w_looked) atomicAdd(&cnt[4], w_looked);
+    if constexpr (kPlane)
+      if (n_unor) atomicAdd(&cnt[5], (unsigned long long)n_unor);
   }
   __shared__ double sw[kAlignWaves][NG];
   __shared__ double sq[kGroups][NG];
@@ -1133,7 +1182,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restric
     for (int j = 1; j < kGroups; ++j) s += sq[j][e];
     host_store(out + e, s);
     if (e == NG - 1) host_store(out + NG, 0.5 * s);
-  } else if (threadIdx.x >= 32 && threadIdx.x < 37) {  // (wave 0 too: it publishes what it stored)
+  } else if (threadIdx.x >= 32 && threadIdx.x < 32 + Rows::kCounters) {  // (wave 0 too: it publishes what it stored)
     const int k = threadIdx.x - 32;
     host_store(reinterpret_cast<unsigned long long*>(out) + kAlignOutCounts + k,
                __hip_atomic_load(cnt + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -1141,6 +1190,155 @@ __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restric
   if (threadIdx.x == 0) {
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     publish_flag(flag, seq);
+  }
+}
+
+// ---- surface normals (DESIGN.md §Dense map, Normals; include/fmx/fmx.h, fmx_normals_build).
+// One record per table slot from the table as it stands: read only, one launch per build.
+//
+// One lane per slot, a grid stride over the slots (the grid is capped like the downloads').  A
+// lane whose slot holds a solid voxel walks the whole cube around the voxel's own cell with
+// cube_visit (the offset list in its order, FMX_NEAREST_AHEAD key loads in flight, no early
+// stop: every cell counts) and adds each admitted neighbour's e = q - q0 into k, S1 and S2 in
+// that order: the sums depend on the offset list alone, not on the order lanes run in.  Then the
+// covariance, smallest_eigvec's cyclic Jacobi on it in fp64, the sign rule and the class.  Every
+// occupied slot's record is written (a filtered voxel's is all zeros: a later search under a
+// wider filter may name it); an empty slot's is not, and is never read: while the snapshot is
+// current the same slots are empty, and k_align and the download index occupied slots only
+// (the writes of a mostly empty table were most of the build's bytes).  The lanes of empty slots, half the table and more,
+// idle through the walk: not compacted (the walk's loads, not the lanes, bound the launch; see
+// DESIGN.md).  No LDS, no scratch, no dynamically indexed array; the counters get one
+// return-less atomic per wave and counter.
+struct NormalsArgs {
+  uint32_t reach, min_support;
+  double max_d2, max_flat;
+};
+constexpr int kNormalOriented = 0, kNormalFlat = 1, kNormalSparse = 2, kNormalFiltered = 3;
+
+// cnt: {oriented, flat_rejected, sparse, filtered, lookups}, zeroed by the caller
+__global__ __launch_bounds__(kDenseThreads) void k_normals_build(const unsigned long long* __restrict__ keys,
+                                                                 const uint32_t* __restrict__ hits,
+                                                                 const double* __restrict__ xyz, uint64_t slots,
+                                                                 DenseTake tk, NormalsArgs na,
+                                                                 const uint32_t* __restrict__ offs,
+                                                                 float4* __restrict__ nrm, uint32_t* __restrict__ support,
+                                                                 unsigned long long* __restrict__ cnt) {
+  const uint32_t slot_mask = (uint32_t)(slots - 1);
+  const uint32_t side = 2u * na.reach + 1u, cells = side * side * side;
+  unsigned long long looked = 0;
+  uint32_t n_cls[4] = {0, 0, 0, 0};  // (the same in every lane of the wave)
+  for (uint64_t base = (uint64_t)blockIdx.x * kDenseThreads; base < slots; base += (uint64_t)gridDim.x * kDenseThreads) {
+    const uint64_t s = base + threadIdx.x;
+    const unsigned long long key0 = s < slots ? keys[s] : kDenseEmpty;
+    int cls = -1;  // empty, or past the end
+    float4 rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    uint32_t k = 0;
+    if (key0 != kDenseEmpty) {
+      cls = kNormalFiltered;
+      if (dense_take(tk, hits[s], s)) {
+        const int c0 = (int)((key0 >> 42) & 0x1FFFFFull) - (int)kDenseBias, c1 = (int)((key0 >> 21) & 0x1FFFFFull) - (int)kDenseBias,
+                  c2 = (int)(key0 & 0x1FFFFFull) - (int)kDenseBias;
+        const double q0 = xyz[3 * s + 0], q1 = xyz[3 * s + 1], q2 = xyz[3 * s + 2];
+        double s1x = 0.0, s1y = 0.0, s1z = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+        cube_visit<1u>(0u, cells, 0u, c0, c1, c2, slot_mask, tk, offs, keys, hits, looked,
+                       [&](unsigned long long, uint32_t slot) {
+                         const double e0 = xyz[3 * (size_t)slot + 0] - q0, e1 = xyz[3 * (size_t)slot + 1] - q1,
+                                      e2 = xyz[3 * (size_t)slot + 2] - q2;
+                         const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+                         if (d2 <= na.max_d2) {
+                           ++k;
+                           s1x += e0, s1y += e1, s1z += e2;
+                           sxx += e0 * e0, sxy += e0 * e1, sxz += e0 * e2;
+                           syy += e1 * e1, syz += e1 * e2, szz += e2 * e2;
+                         }
+                       });
+        const double kd = (double)k;  // (k >= 1: the voxel admits itself)
+        const double m0 = s1x / kd, m1 = s1y / kd, m2 = s1z / kd;
+        double C[3][3];
+        C[0][0] = sxx / kd - m0 * m0;
+        C[0][1] = C[1][0] = sxy / kd - m0 * m1;
+        C[0][2] = C[2][0] = sxz / kd - m0 * m2;
+        C[1][1] = syy / kd - m1 * m1;
+        C[1][2] = C[2][1] = syz / kd - m1 * m2;
+        C[2][2] = szz / kd - m2 * m2;
+        double n[3], lam[3];
+        smallest_eigvec(C, n, lam);
+        // l0 <= l1 <= l2 without an indexed array
+        const double lo01 = fmin(lam[0], lam[1]), hi01 = fmax(lam[0], lam[1]);
+        const double l0r = fmin(lo01, lam[2]), l1 = fmax(lo01, fmin(hi01, lam[2]));
+        const double l0 = l0r < 0.0 ? 0.0 : l0r;
+        const double flat = l1 > 0.0 ? l0 / l1 : (double)INFINITY;
+        rec.w = (float)flat;
+        cls = k < na.min_support ? kNormalSparse : (l1 > 0.0 && l0 <= na.max_flat * l1) ? kNormalOriented : kNormalFlat;
+        if (cls == kNormalOriented) {
+          // the component of largest magnitude is positive, the lowest axis among equal ones
+          const double a0 = fabs(n[0]), a1 = fabs(n[1]), a2 = fabs(n[2]);
+          const double lead = (a0 >= a1 && a0 >= a2) ? n[0] : (a1 >= a2 ? n[1] : n[2]);
+          const double sg = lead < 0.0 ? -1.0 : 1.0;
+          rec.x = (float)(sg * n[0]);
+          rec.y = (float)(sg * n[1]);
+          rec.z = (float)(sg * n[2]);
+        }
+      }
+    }
+    if (cls >= 0) {
+      nrm[s] = rec;
+      support[s] = k;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) n_cls[j] += (uint32_t)__popcll(__ballot(cls == j));
+  }
+  const unsigned long long w_looked = wave_sum(looked);
+  if ((threadIdx.x & 63) == 0) {  // results unused: return-less
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (n_cls[j]) atomicAdd(&cnt[j], (unsigned long long)n_cls[j]);
+    if (w_looked) atomicAdd(&cnt[4], w_looked);
+  }
+}
+
+// The slots a normals download takes (solid under the build's filter; oriented: with a normal)
+// appended to the outputs in no particular order: one returning atomic per wave and step for
+// the wave's place (a download is not a hot path; k_dense_compact's two walks are).  cap: the
+// room in the outputs, which the build's counts sized.
+__global__ __launch_bounds__(kDenseThreads) void k_normals_compact(
+    const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ hits,
+    const unsigned long long* __restrict__ tags, const double* __restrict__ xyz, const float4* __restrict__ nrm,
+    const uint32_t* __restrict__ support, uint64_t slots, DenseTake tk, int oriented, uint32_t cap,
+    uint32_t* __restrict__ out_n, double* __restrict__ o_xyz, unsigned long long* __restrict__ o_tag,
+    uint32_t* __restrict__ o_hits, uint32_t* __restrict__ o_miss, float* __restrict__ o_normal, float* __restrict__ o_flat,
+    uint32_t* __restrict__ o_support) {
+  const int lane = threadIdx.x & 63;
+  for (uint64_t base = (uint64_t)blockIdx.x * kDenseThreads; base < slots; base += (uint64_t)gridDim.x * kDenseThreads) {
+    const uint64_t s = base + threadIdx.x;
+    const uint32_t h = s < slots ? hits[s] : 0u;
+    bool take = s < slots && keys[s] != kDenseEmpty && dense_take(tk, h, s);
+    float4 rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (take) {
+      rec = nrm[s];
+      if (oriented && rec.x == 0.0f && rec.y == 0.0f && rec.z == 0.0f) take = false;
+    }
+    const unsigned long long b = __ballot(take);
+    if (!b) continue;  // (the whole wave)
+    uint32_t at = 0;
+    if (lane == 0) at = atomicAdd(out_n, (uint32_t)__popcll(b));
+    at = (uint32_t)__shfl((int)at, 0, 64);
+    if (take) {
+      const uint32_t o = at + (uint32_t)__popcll(b & lanemask_lt());
+      if (o < cap) {  // (the build's counts sized the outputs: never false)
+        o_xyz[3 * (size_t)o + 0] = xyz[3 * s + 0];
+        o_xyz[3 * (size_t)o + 1] = xyz[3 * s + 1];
+        o_xyz[3 * (size_t)o + 2] = xyz[3 * s + 2];
+        o_tag[o] = tags[s];
+        o_hits[o] = h;
+        if (o_miss) o_miss[o] = dense_misses(tk, s);
+        o_normal[3 * (size_t)o + 0] = rec.x;
+        o_normal[3 * (size_t)o + 1] = rec.y;
+        o_normal[3 * (size_t)o + 2] = rec.z;
+        o_flat[o] = rec.w;
+        o_support[o] = support[s];
+      }
+    }
   }
 }
 
@@ -1404,8 +1602,10 @@ void run_nearest(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34
 
 size_t align_partials() { return (size_t)kNearestBlocks * kAlignLd; }
 
-void run_align(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const double* pose34, const ProbeFilter& f,
-               uint32_t reach, double max_dist2, double sigma, uint32_t seq, hipStream_t st) {
+template <class Rows>
+static void launch_align(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const double* pose34,
+                         const ProbeFilter& f, uint32_t reach, double max_dist2, double sigma, uint32_t seq, hipStream_t st,
+                         Rows rows) {
   auto& D = c->dense;
   auto& N = D.nearest;
   auto& A = D.align;
@@ -1421,11 +1621,72 @@ void run_align(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const 
   FMX_HIP(hipMemsetAsync(A.cnt.p, 0, 8 * sizeof(unsigned long long), st));
   // DESIGN.md §Dense map, Aligning: run_nearest's model without the per-point outputs (the
   // point, 16, and the own cell's key word, 8; the other lookups are not known at launch), plus
-  // the block partials written and read back (28 doubles each way)
+  // the block partials written and read back (28 doubles each way); the plane form's 16 B per
+  // found point are not known at launch
   ProfScope ps(c->prof, PROF_DENSE, (double)m * 24.0 + (double)blocks * 2.0 * 28.0 * sizeof(double), st);
-  hipLaunchKernelGGL(k_align, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)m, every, a, probe_take_args(c, f),
-                     reach, max_dist2, 1.0 / sigma, N.offs.p, D.keys.p, D.hits.p, D.xyz.p, A.cnt.p, A.bpart.p, A.ticket.p,
-                     A.h_out.d, c->h_flag.d, seq);
+  hipLaunchKernelGGL(k_align<Rows>, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)m, every, a,
+                     probe_take_args(c, f), reach, max_dist2, 1.0 / sigma, N.offs.p, D.keys.p, D.hits.p, D.xyz.p, A.cnt.p,
+                     A.bpart.p, A.ticket.p, A.h_out.d, c->h_flag.d, seq, rows);
+  FMX_HIP(hipGetLastError());
+}
+
+void run_align(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const double* pose34, const ProbeFilter& f,
+               uint32_t reach, double max_dist2, double sigma, uint32_t seq, hipStream_t st) {
+  launch_align(c, d_pts, n, every, pose34, f, reach, max_dist2, sigma, seq, st, PointRows{});
+}
+
+void run_plane(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const double* pose34, const ProbeFilter& f,
+               uint32_t reach, double max_dist2, double sigma, uint32_t seq, hipStream_t st) {
+  launch_align(c, d_pts, n, every, pose34, f, reach, max_dist2, sigma, seq, st, PlaneRows{c->dense.normals.nrm.p});
+}
+
+// The build's filter; the miss array wherever it exists (the download reports misses from it).
+static DenseTake normals_take_args(const fmx_ctx* c, const fmx_normals_params& prm) {
+  return probe_take_args(c, probe_filter(prm.min_hits, prm.miss_num, prm.miss_den));
+}
+static uint32_t scan_blocks(uint64_t slots) {
+  return (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (slots + kDenseThreads - 1) / kDenseThreads);
+}
+
+void run_normals_build(fmx_ctx* c, const fmx_normals_params& prm, hipStream_t st) {
+  auto& D = c->dense;
+  auto& N = D.nearest;
+  auto& M = D.normals;
+  if (!N.have) {  // the cube's offsets in shell order, once per context (shared with run_nearest)
+    FMX_HIP(hipMemcpyAsync(N.offs.p, N.h_offs.data(), N.h_offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    N.have = true;
+  }
+  const NormalsArgs na{prm.reach, normals_min_support(prm), prm.max_dist2, prm.max_flatness};
+  FMX_HIP(hipMemsetAsync(M.cnt.p, 0, 8 * sizeof(unsigned long long), st));
+  // DESIGN.md §Dense map, Normals: every slot's key word read (8); per voxel its hits and point
+  // (4 + 24), the own cell's key word (8) and its record written (20); the other cells' 8 B per
+  // lookup, + 4 per present and + 24 per solid neighbour, are not known at launch (the call's
+  // own `lookups` gives the first)
+  ProfScope ps(c->prof, PROF_DENSE, (double)D.slots * 8.0 + (double)D.voxels * 56.0, st);
+  hipLaunchKernelGGL(k_normals_build, dim3(scan_blocks(D.slots)), dim3(kDenseThreads), 0, st, D.keys.p, D.hits.p, D.xyz.p,
+                     D.slots, normals_take_args(c, prm), na, N.offs.p, M.nrm.p, M.support.p, M.cnt.p);
+  FMX_HIP(hipGetLastError());
+}
+
+void run_normals_compact(fmx_ctx* c, const fmx_normals_params& prm, bool oriented_only, bool with_misses, uint32_t count,
+                         hipStream_t st) {
+  auto& D = c->dense;
+  auto& M = D.normals;
+  D.o_xyz.ensure(3 * (size_t)count);
+  D.o_tag.ensure(count);
+  D.o_hits.ensure(count);
+  M.o_normal.ensure(3 * (size_t)count);
+  M.o_flat.ensure(count);
+  M.o_support.ensure(count);
+  uint32_t* o_miss = with_misses && D.carve.have ? D.carve.o_miss.p : nullptr;
+  FMX_HIP(hipMemsetAsync(D.out_n.p, 0, sizeof(uint32_t), st));
+  // every slot's key word, hit count and record (8 + 4 + 16; short-circuits not counted) + per
+  // voxel taken its tag and point read and written, its hits, normal, flatness and support
+  // written (2 * (8 + 24) + 4 + 12 + 4 + 4 + 4 read for the support)
+  ProfScope ps(c->prof, PROF_DENSE, (double)D.slots * 28.0 + (double)count * (o_miss ? 96.0 : 92.0), st);
+  hipLaunchKernelGGL(k_normals_compact, dim3(scan_blocks(D.slots)), dim3(kDenseThreads), 0, st, D.keys.p, D.hits.p, D.tags.p,
+                     D.xyz.p, M.nrm.p, M.support.p, D.slots, normals_take_args(c, prm), oriented_only ? 1 : 0, count,
+                     D.out_n.p, D.o_xyz.p, D.o_tag.p, D.o_hits.p, o_miss, M.o_normal.p, M.o_flat.p, M.o_support.p);
   FMX_HIP(hipGetLastError());
 }
 

@@ -891,62 +891,7 @@ __global__ __launch_bounds__(256) void k_closest(const float4* __restrict__ scan
   if (lane == 0) closest[(size_t)r * cap + slot] = make_int2(res[0], res[1]);
 }
 
-// Cyclic Jacobi on the symmetric 3x3 covariance in double; returns the unit
-// eigenvector of the smallest eigenvalue (Eigen::SelfAdjointEigenSolver col(0)).
-__device__ __forceinline__ void smallest_eigvec(const float cov[3][3], double n[3]) {
-  double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) A[i][j] = (double)cov[i][j];
-  for (int sweep = 0; sweep < 64; ++sweep) {
-    const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-    const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-    if (off <= 1e-36 * dia || off == 0.0) break;
-#pragma unroll
-    for (int pp = 0; pp < 2; ++pp) {
-#pragma unroll
-      for (int qq = pp + 1; qq < 3; ++qq) {
-        const double apq = A[pp][qq];
-        if (apq == 0.0) continue;
-        const double theta = (A[qq][qq] - A[pp][pp]) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double cc = 1.0 / sqrt(t * t + 1.0), ss = t * cc;
-#pragma unroll
-        for (int m = 0; m < 3; ++m) {
-          const double amp = A[m][pp], amq = A[m][qq];
-          A[m][pp] = cc * amp - ss * amq;
-          A[m][qq] = ss * amp + cc * amq;
-        }
-#pragma unroll
-        for (int m = 0; m < 3; ++m) {
-          const double apm = A[pp][m], aqm = A[qq][m];
-          A[pp][m] = cc * apm - ss * aqm;
-          A[qq][m] = ss * apm + cc * aqm;
-        }
-#pragma unroll
-        for (int m = 0; m < 3; ++m) {
-          const double vmp = V[m][pp], vmq = V[m][qq];
-          V[m][pp] = cc * vmp - ss * vmq;
-          V[m][qq] = ss * vmp + cc * vmq;
-        }
-      }
-    }
-  }
-  int mi = 0;  // first smallest diagonal entry (no dynamic indexing: no scratch)
-  double dm = A[0][0];
-  if (A[1][1] < dm) {
-    mi = 1;
-    dm = A[1][1];
-  }
-  if (A[2][2] < dm) mi = 2;
-  double v0 = mi == 0 ? V[0][0] : (mi == 1 ? V[0][1] : V[0][2]);
-  double v1 = mi == 0 ? V[1][0] : (mi == 1 ? V[1][1] : V[1][2]);
-  double v2 = mi == 0 ? V[2][0] : (mi == 1 ? V[2][1] : V[2][2]);
-  const double nn = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
-  n[0] = v0 / nn;
-  n[1] = v1 / nn;
-  n[2] = v2 / nn;
-}
-
+// (smallest_eigvec, the cyclic Jacobi on the 3 x 3 covariance, is in fmx_device.hpp)
 // compute_normal (extraction.tpp:263-329): one lane per selected planar point.
 __device__ int fit_one(const float4* __restrict__ scan, const uint32_t* __restrict__ sel_slots,
                        const int2* __restrict__ closest, const ExArgs& a, float4* __restrict__ nrm_slots,

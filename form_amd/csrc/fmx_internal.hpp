@@ -23,6 +23,7 @@
 #include "probe_host.hpp"
 #include "nearest_host.hpp"
 #include "align_host.hpp"
+#include "normals_host.hpp"
 #include "upload_host.hpp"
 #include "stage.hpp"
 #include "store_plan.hpp"
@@ -682,6 +683,23 @@ struct fmx_ctx {
       fmx::DBuf<uint32_t> ticket;
       fmx::HBuf<double> h_out;
     } align;
+    // surface normals (fmx_normals_*, read by fmx_plane_*; densemap.hip, the normals block):
+    // one snapshot per build, exactly `slots` entries each (+ 20 B per slot): {n0, n1, n2,
+    // flatness} and the support.  `current` is the one host-side flag every call that changes
+    // the table clears (normals_stale in dense_api.cpp).  Nothing here is allocated, and
+    // nothing launched, unless fmx_normals_build is called
+    struct Normals {
+      bool built = false, current = false;
+      uint64_t voxels = 0, oriented = 0, solid = 0;  // at the build
+      fmx_normals_params prm{};                      // ... and its parameters (the download's filter)
+      fmx::DBuf<float4> nrm;
+      fmx::DBuf<uint32_t> support;
+      fmx::DBuf<unsigned long long> cnt;  // {oriented, flat_rejected, sparse, filtered, lookups}; zeroed by each build
+      fmx::HBuf<unsigned long long> h_cnt;
+      // download: beside o_xyz / o_tag / o_hits
+      fmx::DBuf<float> o_normal, o_flat;
+      fmx::DBuf<uint32_t> o_support;
+    } normals;
     // loading voxels back (fmx_upload_voxels; densemap.hip, the upload block): the device copies
     // of a call's entries, grown at first use; nothing below is allocated, and nothing
     // launched, unless that entry point is called
@@ -1087,6 +1105,19 @@ void run_nearest(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34
 size_t align_partials();
 void run_align(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const double* pose34, const ProbeFilter& f,
                uint32_t reach, double max_dist2, double sigma, uint32_t seq, hipStream_t st);
+// ... the same with the point-to-plane row against c->dense.normals.nrm (k_align's second
+// instantiation; the six counters' bits from word 32 of h_out, unoriented last)
+void run_plane(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const double* pose34, const ProbeFilter& f,
+               uint32_t reach, double max_dist2, double sigma, uint32_t seq, hipStream_t st);
+// ... normals: one record per slot into c->dense.normals.nrm / support (exactly `slots` entries
+// each, allocated by the caller, as c->dense.nearest.offs and normals.cnt), the five counts
+// into normals.cnt, which the call zeroes first (one launch, queued; reads the table only);
+// then the `count` voxels solid under prm's filter (oriented_only: with a normal) appended to
+// c->dense.o_* (and carve.o_miss with with_misses) and normals.o_*, which the call sizes (one
+// launch, queued)
+void run_normals_build(fmx_ctx* c, const fmx_normals_params& prm, hipStream_t st);
+void run_normals_compact(fmx_ctx* c, const fmx_normals_params& prm, bool oriented_only, bool with_misses, uint32_t count,
+                         hipStream_t st);
 // ... rolling: {inside, outside} of the box of voxels |v - cc| <= half (one launch, waits for
 // it); then, with c->dense.o_* sized to `evicted` and c->dense.roll.s_* to `kept`, the evicted
 // voxels appended to o_*, the kept ones put back into the emptied table and the device's

@@ -176,6 +176,40 @@ class _AlignResult(C.Structure):
                 ("counts", _AlignCounts)]
 
 
+class _NormalsParams(C.Structure):
+    _fields_ = [("min_hits", C.c_uint32), ("miss_num", C.c_uint32), ("miss_den", C.c_uint32), ("reach", C.c_uint32),
+                ("max_dist2", C.c_double), ("min_support", C.c_uint32), ("max_flatness", C.c_double)]
+
+
+class _NormalsCounts(C.Structure):
+    _fields_ = [("oriented", C.c_uint32), ("flat_rejected", C.c_uint32), ("sparse", C.c_uint32), ("filtered", C.c_uint32),
+                ("lookups", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(oriented=int(self.oriented), flat_rejected=int(self.flat_rejected), sparse=int(self.sparse),
+                    filtered=int(self.filtered), lookups=int(self.lookups))
+
+
+class _PlaneCounts(C.Structure):
+    _fields_ = [("found", C.c_uint32), ("none", C.c_uint32), ("out_of_range", C.c_uint32), ("invalid", C.c_uint32),
+                ("skipped", C.c_uint32), ("unoriented", C.c_uint32), ("lookups", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(found=int(self.found), none=int(self.none), out_of_range=int(self.out_of_range),
+                    invalid=int(self.invalid), skipped=int(self.skipped), unoriented=int(self.unoriented),
+                    lookups=int(self.lookups))
+
+
+class _PlaneResult(C.Structure):
+    _fields_ = [("iters", C.c_uint32), ("converged", C.c_int32), ("last_step", C.c_double), ("error", C.c_double),
+                ("counts", _PlaneCounts)]
+
+
+# FORM.dense_localize(plane=True) and FORM.dense_normals build the snapshot with these when it is
+# not current: the 3 x 3 x 3 cells around a voxel, at least 5 neighbours, l0 <= 0.1 l1
+NORMALS_DEFAULTS = dict(reach=1, max_dist=None, min_support=5, max_flatness=0.1)
+
+
 # fmx_probe_points / fmx_probe_rays: the per-point state
 PROBE_ABSENT, PROBE_FILTERED, PROBE_SOLID, PROBE_OUT_OF_RANGE, PROBE_INVALID = range(5)
 PROBE_NO_STEP = 0xFFFFFFFF
@@ -244,6 +278,8 @@ EXPORTED = [
     "fmx_upload_voxels",
     "fmx_nearest_voxels",
     "fmx_align_system", "fmx_align_dense",
+    "fmx_normals_build", "fmx_normals_stats", "fmx_normals_download",
+    "fmx_plane_system", "fmx_plane_align",
 ]
 
 PAIR_SORT_FORMS = ("none", "per-block", "tail-scanned", "scatter-scanned")
@@ -1034,25 +1070,83 @@ class Context:
         del keep
         return out, cnt.as_dict()
 
+    def plane_system(self, points, pose34, reach: int = 1, max_dist=None, sigma: float = 1.0, min_hits: int = 1,
+                     max_miss_ratio=None, stride: int = 1):
+        """fmx_plane_system: align_system with the point-to-plane row against the winner's
+        normal of the current snapshot (normals_build); a winner without a normal makes the
+        point unoriented and adds nothing.  Returns (system, counts) as align_system, the
+        counts with unoriented."""
+        prm = self._align_params(reach, max_dist, sigma, min_hits, max_miss_ratio, stride)
+        on_dev, ptr, n, keep = _scan_ptr(points)
+        pose = np.ascontiguousarray(pose34, np.float64).reshape(12)
+        if on_dev:
+            _ready(keep)
+        out = np.zeros(29, np.float64)
+        cnt = _PlaneCounts()
+        self._chk(self._L.fmx_plane_system(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev), _p(pose),
+                                           C.byref(prm), _p(out), C.byref(cnt)))
+        del keep
+        return out, cnt.as_dict()
+
     def dense_align(self, points, pose_init34, reach: int = 1, max_dist=None, sigma: float = 1.0, min_hits: int = 1,
-                    max_miss_ratio=None, stride: int = 1, max_iters: int = 30, threshold: float = 1e-6) -> dict:
+                    max_miss_ratio=None, stride: int = 1, max_iters: int = 30, threshold: float = 1e-6,
+                    plane: bool = False) -> dict:
         """fmx_align_dense: Gauss-Newton on align_system's system from pose_init34 (arguments as
         align_system), at most max_iters systems, until a step's norm is below threshold;
         changes nothing.  Returns pose (3, 4), iters, converged, last_step, error and counts
-        (the last system's)."""
+        (the last system's).  plane=True: fmx_plane_align, the same loop on plane_system's
+        system (needs a current normals_build)."""
         prm = self._align_params(reach, max_dist, sigma, min_hits, max_miss_ratio, stride)
         on_dev, ptr, n, keep = _scan_ptr(points)
         pose = np.ascontiguousarray(pose_init34, np.float64).reshape(12)
         if on_dev:
             _ready(keep)
         out = np.zeros(12, np.float64)
-        res = _AlignResult()
-        self._chk(self._L.fmx_align_dense(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev), _p(pose),
-                                          C.byref(prm), C.c_uint32(max_iters), C.c_double(threshold), _p(out),
-                                          C.byref(res)))
+        res = _PlaneResult() if plane else _AlignResult()
+        call = self._L.fmx_plane_align if plane else self._L.fmx_align_dense
+        self._chk(call(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev), _p(pose), C.byref(prm),
+                       C.c_uint32(max_iters), C.c_double(threshold), _p(out), C.byref(res)))
         del keep
         return dict(pose=out.reshape(3, 4), iters=int(res.iters), converged=bool(res.converged),
                     last_step=float(res.last_step), error=float(res.error), counts=res.counts.as_dict())
+
+    # ---------------------------------------------------------------- surface normals of the map
+    def normals_build(self, reach: int = 1, max_dist=None, min_support: int = 5, max_flatness: float = 0.1,
+                      min_hits: int = 1, max_miss_ratio=None) -> dict:
+        """fmx_normals_build: one normal record per voxel of the map as it stands, from the
+        solid representatives (min_hits, max_miss_ratio) of the cells within `reach` of the
+        voxel's own, no farther than max_dist (None: the whole cube): the covariance's smallest
+        eigenvector where at least min_support were admitted and l0 <= max_flatness * l1.  The
+        snapshot is current until the table changes.  Returns the counts oriented,
+        flat_rejected, sparse, filtered (they sum to the voxels) and lookups."""
+        num, den = miss_fraction(max_miss_ratio)
+        md = math.inf if max_dist is None else float(max_dist)
+        prm = _NormalsParams(min_hits, num, den, reach, md * md, min_support, float(max_flatness))
+        cnt = _NormalsCounts()
+        self._chk(self._L.fmx_normals_build(self.h, C.byref(prm), C.byref(cnt)))
+        return cnt.as_dict()
+
+    def normals_stats(self) -> dict:
+        """fmx_normals_stats: built, current, and the voxels and the oriented ones at the build."""
+        s = np.zeros(4, np.uint64)
+        self._chk(self._L.fmx_normals_stats(self.h, _p(s)))
+        return dict(built=bool(s[0]), current=bool(s[1]), voxels=int(s[2]), oriented=int(s[3]))
+
+    def normals_download(self, oriented_only: bool = True, misses=None) -> dict:
+        """fmx_normals_download: dense_download's arrays for the voxels that were solid under
+        the build's filter (oriented_only: those with a normal), in no particular order, with
+        normals (N, 3) float32 (zeros unless oriented), flatness (N,) float32 and support (N,)
+        uint32.  The snapshot must be current."""
+        flag = C.c_int(int(bool(oriented_only)))
+        n = C.c_uint32(0)
+        self._chk(self._L.fmx_normals_download(self.h, flag, None, None, None, None, C.byref(n)))
+        m = int(n.value)
+        A, out = self._voxel_arrays(m, self._with_misses(misses))
+        out.update(normals=np.zeros((m, 3), np.float32), flatness=np.zeros(m, np.float32), support=np.zeros(m, np.uint32))
+        if m:
+            self._chk(self._L.fmx_normals_download(self.h, flag, C.byref(A), _p(out["normals"]), _p(out["flatness"]),
+                                                   _p(out["support"]), C.byref(n)))
+        return {k: v[:n.value] for k, v in out.items()}
 
     # ---------------------------------------------------------------- loading voxels back
     def dense_upload(self, points, scan=None, index=None, hits=None, misses=None) -> dict:
@@ -1597,6 +1691,32 @@ class FORM:
             return out
         return self._est.dense_download(min_hits, max_miss_ratio)
 
+    def dense_normals(self, min_hits: int = 1, max_miss_ratio=None, reach_m=None, viewpoint=None) -> dict:
+        """The dense map's oriented voxels with their surface normals (Context.normals_build,
+        then normals_download): dense_map's arrays plus normals (N, 3) float32, flatness and
+        support.  The snapshot is rebuilt with this filter, NORMALS_DEFAULTS and reach =
+        ceil(reach_m / voxel_width) (None: one cell; ValueError past NEAREST_MAX_REACH), which
+        also bounds the neighbours' distance.  A normal's sign is the build's (its largest
+        component positive) unless a viewpoint (3,) is given: each is then flipped, here on
+        the host, to face it."""
+        self._need_dense()
+        kw = dict(NORMALS_DEFAULTS)
+        if reach_m is not None:
+            r = float(reach_m)
+            if not (r > 0.0) or math.isinf(r):
+                raise ValueError("reach_m must be a finite number > 0")
+            kw["reach"] = max(1, math.ceil(r / float(self._dense["voxel_width"])))
+            kw["max_dist"] = r
+            if kw["reach"] > NEAREST_MAX_REACH:
+                raise ValueError(f"reach_m spans more than {NEAREST_MAX_REACH} voxels: reach {kw['reach']}")
+        self._est.normals_build(min_hits=min_hits, max_miss_ratio=max_miss_ratio, **kw)
+        out = self._est.normals_download(True)
+        if viewpoint is not None:
+            to_eye = np.asarray(viewpoint, np.float64).reshape(1, 3) - out["points"]
+            away = np.einsum("ij,ij->i", to_eye, out["normals"].astype(np.float64)) < 0.0
+            out["normals"][away] *= -1.0
+        return out
+
     def _probe_args(self, points, pose):
         if self._est is None or self._dense is None or not self._dense["enable"]:
             raise RuntimeError("the dense map is off (set_dense_map, then initialize())")
@@ -1643,14 +1763,20 @@ class FORM:
         return fitness_of(got["state"], got["dist2"])
 
     def dense_localize(self, points, radius_m: float, pose_guess=None, sigma: float = 0.1, max_iters: int = 30,
-                       threshold: float = 1e-6, stride: int = 1, min_hits: int = 1, max_miss_ratio=None) -> dict:
+                       threshold: float = 1e-6, stride: int = 1, min_hits: int = 1, max_miss_ratio=None,
+                       plane: bool = False) -> dict:
         """Register a scan against the dense map (Context.dense_align; points as dense_lookup,
         pose_guess None: the current pose): point-to-point Gauss-Newton on the nearest solid
         voxels within radius_m (reach as dense_nearest, ValueError past NEAREST_MAX_REACH).
         Nothing is changed, the estimator included.  Returns pose (3, 4), iters, converged
         and, from one more system at that pose, n_valid, n_found, fitness = n_found / n_valid
         and rmse = sqrt(2 error sigma^2 / n_found) (0.0 where the divisor is 0): dense_fitness's
-        figures over the points i % stride == 0, without a per-point download."""
+        figures over the points i % stride == 0, without a per-point download.
+        plane=True: point-to-plane against the map's normals (Context.plane_system); the
+        snapshot is built first with NORMALS_DEFAULTS and this call's filter when
+        normals_stats() says it is not current.  n_found then counts the points with an
+        oriented winner, n_valid those and the unoriented and the ones without a winner, rmse
+        is the point-to-plane one, and n_unoriented is returned as well."""
         points, T = self._probe_args(points, pose_guess)
         r = float(radius_m)
         if not (r >= 0.0) or math.isinf(r):
@@ -1658,6 +1784,16 @@ class FORM:
         reach = math.floor(r / float(self._dense["voxel_width"])) + 1
         if reach > NEAREST_MAX_REACH:
             raise ValueError(f"radius_m spans more than {NEAREST_MAX_REACH} voxels: reach {reach}")
+        if plane:
+            if not self._est.normals_stats()["current"]:
+                self._est.normals_build(min_hits=min_hits, max_miss_ratio=max_miss_ratio, **NORMALS_DEFAULTS)
+            got = self._est.dense_align(points, T, reach, r, sigma, min_hits, max_miss_ratio, stride, max_iters, threshold,
+                                        plane=True)
+            S, cnt = self._est.plane_system(points, got["pose"], reach, r, sigma, min_hits, max_miss_ratio, stride)
+            n_found, n_valid = cnt["found"], cnt["found"] + cnt["unoriented"] + cnt["none"]
+            return dict(pose=got["pose"], iters=got["iters"], converged=got["converged"], n_valid=n_valid,
+                        n_found=n_found, n_unoriented=cnt["unoriented"], fitness=n_found / n_valid if n_valid else 0.0,
+                        rmse=math.sqrt(2.0 * float(S[28]) * float(sigma) * float(sigma) / n_found) if n_found else 0.0)
         got = self._est.dense_align(points, T, reach, r, sigma, min_hits, max_miss_ratio, stride, max_iters, threshold)
         S, cnt = self._est.align_system(points, got["pose"], reach, r, sigma, min_hits, max_miss_ratio, stride)
         n_found, n_valid = cnt["found"], cnt["found"] + cnt["none"]

@@ -872,6 +872,105 @@ fmx_status fmx_align_dense(fmx_ctx* ctx, const float* xyzw, size_t n_points, int
                            const double pose_init34[12], const fmx_align_params* params, uint32_t max_iters,
                            double threshold, double pose_out34[12], fmx_align_result* result /* may be NULL */);
 
+/* ---------------- surface normals of the dense map: one snapshot per build ---------------
+ * A per-voxel normal field computed on the device from the map's solid representatives, kept
+ * beside the table, one record per table slot: the normal (3 floats) and the flatness (1 float)
+ * in one 16-byte word, and the support (uint32): 20 bytes per slot on top of the table's 44 (52
+ * with carving), allocated at the first fmx_normals_build (DESIGN.md §Dense map, Normals;
+ * tests/normals_ref.py restates it).  The build only reads the table.
+ * Semantics, fp64 without contraction.  For every stored voxel with representative q0:
+ *   filtered  not solid under fmx_carve_download's rule with params' min_hits, miss_num,
+ *             miss_den: support 0, no normal;
+ *   support   otherwise the neighbours are the present and solid voxels of the cells within
+ *             `reach` of the voxel's own cell (the cell its key names), the own cell included,
+ *             cells that cannot be stored skipped as in fmx_nearest_voxels.  A neighbour with
+ *             representative q has e = q - q0 and d2 = (e_0 e_0 + e_1 e_1) + e_2 e_2 and is
+ *             admitted iff d2 <= max_dist2 (+inf: the whole cube); support = k, the number
+ *             admitted (k >= 1: the voxel admits itself);
+ *   moments   S1 = sum e, S2 = sum e e^T (six entries), m = S1 / k, C_ab = S2_ab / k - m_a m_b;
+ *             l0 <= l1 <= l2 the eigenvalues of C (cyclic Jacobi in fp64), a negative l0 read
+ *             as 0; n the unit eigenvector of l0, its sign such that the component of largest
+ *             magnitude is positive (the lowest axis among equal magnitudes: nothing in the
+ *             table knows where the sensor was); flatness = l0 / l1, +inf when l1 <= 0;
+ *   class     sparse when k < max(min_support, 3); else oriented iff l1 > 0 and l0 <=
+ *             max_flatness * l1; else flat_rejected;
+ *   stored    n rounded once to fp32, all zeros unless oriented; flatness as fp32 (0 for a
+ *             filtered voxel); support.
+ * The order of each voxel's sums is the kernel's (the cube's cells in the fixed order of the
+ * offset list, one lane per voxel), not the order the threads run in: two builds of the same
+ * table with the same parameters store the same bits.  counts->lookups is the number of cells
+ * looked up, a diagnostic as fmx_nearest_counts'.  One launch on the context stream; the call
+ * returns once the counts are in.  An empty map launches nothing and gives zero counts.
+ * Staleness.  The snapshot is indexed by slot: it is current from a successful build until the
+ * next call that changed, or may have changed, the table: a successful fmx_dense_integrate or
+ * register-path integration (with or without its carve), fmx_carve_rays, fmx_upload_voxels with
+ * n > 0, any roll that evicts, fmx_dense_clear, and fmx_dense_configure, which also drops the
+ * arrays.  fmx_normals_stats gives {built, current, voxels at the build, oriented at the
+ * build}, all 0 when never built, FMX_OK on any context.
+ * fmx_normals_download follows fmx_carve_download's two-call protocol (all pointers NULL: *n
+ * receives the size; otherwise *n is the capacity on entry, FMX_E_SIZE with nothing written if
+ * too small, and the count on return): the voxels that were solid under the build's filter, or
+ * with oriented_only != 0 only the oriented ones, in no particular order; normal takes 3
+ * floats per voxel; any pointer may be NULL.
+ * Status codes: FMX_E_STATE unless the dense map is configured and enabled, and, for the
+ * download, unless the snapshot is current; FMX_E_INVAL for NULL params or counts' pointer
+ * where required, reach 0 (the own cell alone supports nothing) or > FMX_NEAREST_MAX_REACH, a
+ * NaN or negative max_dist2, a max_flatness that is not finite and in [0, 1]; FMX_E_OOM when an
+ * array cannot be allocated (a snapshot that was current stays so). */
+typedef struct fmx_normals_params {
+  uint32_t min_hits, miss_num, miss_den;  /* fmx_carve_download's filter */
+  uint32_t reach;                         /* 1 .. FMX_NEAREST_MAX_REACH */
+  double max_dist2;                       /* fmx_nearest_voxels' rule */
+  uint32_t min_support;                   /* values below 3 read as 3 */
+  double max_flatness;                    /* in [0, 1] */
+} fmx_normals_params;
+typedef struct fmx_normals_counts {
+  uint32_t oriented, flat_rejected, sparse, filtered;  /* the four sum to the map's voxels */
+  uint64_t lookups;                                    /* diagnostic, as fmx_nearest_counts */
+} fmx_normals_counts;
+fmx_status fmx_normals_build(fmx_ctx* ctx, const fmx_normals_params* params, fmx_normals_counts* counts /* may be NULL */);
+fmx_status fmx_normals_stats(fmx_ctx* ctx, uint64_t out[4]);
+fmx_status fmx_normals_download(fmx_ctx* ctx, int oriented_only, const fmx_voxel_arrays* arrays, float* normal,
+                                float* flatness, uint32_t* support, uint32_t* n);
+
+/* ---------------- point-to-plane alignment against the dense map's normals ---------------
+ * fmx_align_system / fmx_align_dense with the point-to-plane residual (DESIGN.md §Dense map,
+ * Plane alignment; tests/plane_ref.py restates it).  Skipping, classifying and searching are
+ * fmx_align_system's, word for word: the winner is the nearest solid representative, normals
+ * play no part in the search.  Both calls only read.
+ *   unoriented  a found point whose winner's slot holds no normal (not oriented at the build)
+ *               is counted here, not under found, and contributes nothing;
+ *   row         a found point with sensor-frame point p, world point w, winner q and normal n
+ *               (the stored fp32 widened) contributes one row, the plane factor of
+ *               fmx_linearize with X(i) the identity, p_i = q, n_i = n, p_j = p:
+ *                 r = (n_0 (w_0 - q_0) + n_1 (w_1 - q_1)) + n_2 (w_2 - q_2)
+ *                 H = [m_2 p_1 - m_1 p_2, m_0 p_2 - m_2 p_0, m_1 p_0 - m_0 p_1, m_0, m_1, m_2]
+ *               with m = R^T n;
+ *   output      whitening, packing, out[28], the fixed order of the sums and the bit-for-bit
+ *               repeatability are fmx_align_system's.  The system does not depend on the sign
+ *               of n.
+ * fmx_plane_align is fmx_align_dense's loop over this system; a singular system (e.g. a scan
+ * that sees one plane only) is FMX_E_STATE with pose_out unwritten.
+ * Status codes: fmx_align_system's / fmx_align_dense's, and FMX_E_STATE unless the normal
+ * snapshot is current (fmx_normals_build). */
+typedef struct fmx_plane_counts {
+  uint32_t found, none, out_of_range, invalid, skipped, unoriented;  /* the six sum to n */
+  uint64_t lookups;                                                  /* diagnostic, as fmx_nearest_counts */
+} fmx_plane_counts;
+fmx_status fmx_plane_system(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                            const double pose34[12], const fmx_align_params* params, double out[29],
+                            fmx_plane_counts* counts /* may be NULL */);
+typedef struct fmx_plane_result {
+  uint32_t iters;          /* systems evaluated */
+  int32_t converged;       /* 1 iff the last step's norm < threshold */
+  double last_step;        /* ||dx|| of the last step, 0 when iters == 0 */
+  double error;            /* out[28] of the last system evaluated */
+  fmx_plane_counts counts; /* of the last system evaluated */
+} fmx_plane_result;
+fmx_status fmx_plane_align(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                           const double pose_init34[12], const fmx_align_params* params, uint32_t max_iters,
+                           double threshold, double pose_out34[12], fmx_plane_result* result /* may be NULL */);
+
 /* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
  * pose at the middle of the last registered sweep. */
 fmx_status fmx_current_pose(fmx_ctx* ctx, double pose34[12]);

@@ -1,0 +1,18 @@
+# tests/cpp/test_normals_host: the host-only parts of the dense map's surface normals and of the
+# point-to-plane alignment (form_amd/csrc/normals_host.hpp, no HIP headers), plain g++ -Werror
+# like its neighbours, with the address and undefined-behaviour sanitizers (runtimes linked
+# statically: the program needs nothing preloaded).  -ffp-contract=off: pose.hpp's rounding, as
+# the library builds it.
+# Built by __graft_entry__.build():  make -C tests/cpp -f normals_host.mk
+CXX ?= g++
+ROOT := ../..
+CXXFLAGS ?= -O1 -g -std=c++17 -ffp-contract=off -Wall -Wextra -Werror -fsanitize=address,undefined \
+	-fno-sanitize-recover=all -static-libasan -static-libubsan
+all: test_normals_host
+test_normals_host: test_normals_host.cpp $(ROOT)/form_amd/csrc/normals_host.hpp $(ROOT)/form_amd/csrc/align_host.hpp \
+		$(ROOT)/form_amd/csrc/nearest_host.hpp $(ROOT)/form_amd/csrc/probe_host.hpp $(ROOT)/form_amd/csrc/carve_host.hpp \
+		$(ROOT)/form_amd/csrc/pose.hpp $(ROOT)/include/fmx/fmx.h
+	$(CXX) $(CXXFLAGS) -I$(ROOT)/form_amd/csrc -I$(ROOT)/include -o $@ test_normals_host.cpp
+clean:
+	rm -f test_normals_host
+.PHONY: all clean
