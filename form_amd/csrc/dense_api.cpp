@@ -1,7 +1,8 @@
 // dense_api.cpp — the host layer of the dense voxel map (densemap.hip): every fmx_dense_*,
-// fmx_roll_*, fmx_carve_*, fmx_probe_*, fmx_upload_*, fmx_nearest_*, fmx_align_*, fmx_normals_*
-// and fmx_plane_* entry point of include/fmx/fmx.h, and the four calls register_scan (fmx_api.cpp) makes into the
-// map (fmx_api.hpp).  The argument checks that need no device live in the *_host.hpp headers.
+// fmx_roll_*, fmx_carve_*, fmx_probe_*, fmx_upload_*, fmx_nearest_*, fmx_align_*, fmx_score_*,
+// fmx_normals_* and fmx_plane_* entry point of include/fmx/fmx.h, and the four calls
+// register_scan (fmx_api.cpp) makes into the map (fmx_api.hpp).  The argument checks that need
+// no device live in the *_host.hpp headers.
 // Host code only; built like fmx_api.cpp.
 #include <algorithm>
 #include <cmath>
@@ -839,6 +840,55 @@ fmx_status fmx_align_dense(fmx_ctx* c, const float* xyzw, size_t n, int src_on_d
     std::memcpy(pose_out34, T, sizeof(T));
     if (result) *result = R;
   });
+}
+
+// ---- scoring many candidate poses (score_host.hpp).  The queries' path: the checks, the queue
+// settled, every buffer, the scan staged once; then per chunk the poses staged, two launches and
+// the records' copy out, and one wait at the end.
+fmx_status fmx_score_poses(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double* poses34,
+                           uint32_t n_poses, const fmx_align_params* prm, fmx_pose_score* scores) {
+  return guard<false>(c, [&] {
+    auto& D = c->dense;
+    auto& S = D.score;
+    need_map(c);
+    checked([&](const char** why) {
+      return score_check(xyzw, (unsigned long long)n, poses34, (unsigned long long)n_poses, prm, scores, why);
+    });
+    dense_settle(c);
+    if (!n_poses) return;
+    if (!n) {
+      std::memset(scores, 0, (size_t)n_poses * sizeof(fmx_pose_score));
+      return;
+    }
+    const uint32_t every = align_stride(*prm);
+    const ScorePlan plan = score_plan((unsigned long long)n, every, n_poses);
+    const uint32_t most = std::min(plan.chunk, n_poses);  // the poses of the largest chunk
+    // every buffer before anything is launched or written (FMX_E_OOM when one cannot be had)
+    const auto ensure = [](auto& b, size_t m) { roll_ensure(b, m, "dense map score"); };
+    offsets_ensure(c, "dense map score");
+    ensure(S.poses, (size_t)most * 12);
+    ensure(S.part, (size_t)most * plan.tiles);
+    ensure(S.out, most);
+    if (!src_on_dev) ensure(D.in, n);
+    const float4* d = scan_on_device(c, xyzw, n, src_on_dev);
+    const ProbeFilter f = probe_filter(prm->min_hits, prm->miss_num, prm->miss_den);
+    for (uint32_t k0 = 0; k0 < n_poses; k0 += plan.chunk) {
+      const uint32_t k = std::min(plan.chunk, n_poses - k0);
+      FMX_HIP(hipMemcpyAsync(S.poses.p, poses34 + (size_t)k0 * 12, (size_t)k * 12 * sizeof(double), hipMemcpyHostToDevice,
+                             c->stream));
+      run_score(c, d, n, every, k, f, prm->reach, prm->max_dist2, c->stream);
+      FMX_HIP(hipMemcpyAsync(scores + k0, S.out.p, (size_t)k * sizeof(fmx_pose_score), hipMemcpyDeviceToHost, c->stream));
+    }
+    FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns the points and the poses again
+  });
+}
+
+fmx_status fmx_score_plan(uint64_t n_points, uint32_t stride, uint32_t n_poses, uint32_t out[6]) {
+  if (!out || n_poses > (uint32_t)FMX_SCORE_MAX_POSES || n_points >= (1ull << 32)) return FMX_E_INVAL;
+  const ScorePlan p = score_plan(n_points, stride, n_poses);
+  const uint32_t v[6] = {p.kept, p.tile, p.tiles, p.chunk, p.chunks, p.cap};
+  std::memcpy(out, v, sizeof(v));
+  return FMX_OK;
 }
 
 // ---- surface normals of the dense map (normals_host.hpp)

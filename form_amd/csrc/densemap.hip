@@ -1193,6 +1193,117 @@ __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restric
   }
 }
 
+// ---- scoring candidate poses (DESIGN.md §Dense map, Scoring; include/fmx/fmx.h,
+// fmx_score_poses).  The nearest search of one staged scan at many poses: per pose one 32-byte
+// record (four class counts, the sum of the winners' d2, the lookups), nothing per point.  Read
+// only, two launches per chunk of poses on the context stream.
+//
+// A work item is one pose and one tile of kScoreTile kept points (score_host.hpp; the tile is
+// the block: one lane per kept point, as k_align's FMX_ALIGN_LANES = 1).  The items of a chunk
+// are tile-major (item = tile * poses + pose: neighbouring blocks share a tile's points and take
+// neighbouring poses of the list; FMX_SCORE_TILE_MAJOR=0 builds the pose-major order, 8 to 15 %
+// slower at 1024 poses in tools/score_cost.py --ab: the records are the same bits either way)
+// and a block walks them with a grid stride under k_nearest's cap.  The item's pose comes
+// from the staged pose array and is uniform over the block; the DenseArgs around it goes to
+// probe_classify and nearest_search unchanged.  Reduction, every order fixed: a wave's d2 by
+// wave_sum's xor butterfly (a point that found nothing adds +0.0: exact), its counts by
+// ballots, then the block's waves in wave order through LDS, one partial record per item.
+// k_score_finish then sums a pose's tiles: one wave per pose, lane l takes tiles l, l + 64, ...
+// in that order, then the same butterfly.  Which block ran an item, how many poses the chunk
+// holds and where the pose stands in it enter neither: a record depends on the points, the
+// stride, the search and its own pose alone.  The launch boundary is the hand-off between the
+// two: no ticket, no agent-scope protocol, no floating-point atomic.
+#ifndef FMX_SCORE_TILE_MAJOR
+#define FMX_SCORE_TILE_MAJOR 1
+#endif
+static_assert(kScoreTile == (uint32_t)kDenseThreads, "a tile is one block-wide pass");
+static_assert(kScoreGridCap == (uint32_t)kNearestBlocks, "the score grid is capped as k_nearest's");
+constexpr int kScoreWaves = kDenseThreads / kWave;
+
+// m: the kept points; tiles = ceil(m / kScoreTile); items = poses of the chunk * tiles.
+// part[pose * tiles + tile]: written whole by the item's block.
+__global__ __launch_bounds__(kDenseThreads) void k_score(const float4* __restrict__ pts, uint32_t m, uint32_t every,
+                                                         const double* __restrict__ poses, uint32_t tiles, uint32_t items,
+                                                         DenseArgs a, DenseTake tk, uint32_t reach, double max_d2,
+                                                         const uint32_t* __restrict__ offs,
+                                                         const unsigned long long* __restrict__ keys,
+                                                         const uint32_t* __restrict__ hits,
+                                                         const double* __restrict__ xyz,
+                                                         fmx_pose_score* __restrict__ part) {
+  __shared__ double s_d2[kScoreWaves];
+  __shared__ unsigned long long s_look[kScoreWaves];
+  __shared__ uint32_t s_cnt[kScoreWaves][4];
+  const unsigned long long inf_bits = 0x7FF0000000000000ull;
+  const int w = threadIdx.x / kWave;
+  for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {  // (uniform over the block)
+#if FMX_SCORE_TILE_MAJOR
+    const uint32_t n_poses = items / tiles, tile = item / n_poses, pose = item - tile * n_poses;
+#else
+    const uint32_t pose = item / tiles, tile = item - pose * tiles;
+#endif
+#pragma unroll
+    for (int k = 0; k < 12; ++k) a.T.m[k] = poses[(size_t)pose * 12 + k];
+    const unsigned long long g = (unsigned long long)tile * kScoreTile + threadIdx.x;
+    int cls = -1;  // past the end
+    double p0 = 0.0, p1 = 0.0, p2 = 0.0;
+    int c0 = 0, c1 = 0, c2 = 0;
+    if (g < (unsigned long long)m) {
+      double wp[3];
+      int v[3];
+      cls = probe_classify(pts[g * (unsigned long long)every], a, wp, v);  // (g < m: the index is below n)
+      p0 = wp[0], p1 = wp[1], p2 = wp[2];
+      if (cls == 0) c0 = v[0], c1 = v[1], c2 = v[2];
+    }
+    unsigned long long b_bits = inf_bits, b_key = kDenseEmpty, looked = 0;
+    uint32_t b_slot = kDenseDropped;
+    nearest_search<1u>(cls, p0, p1, p2, c0, c1, c2, 0u, a, tk, reach, max_d2, offs, keys, hits, xyz, b_bits, b_key, b_slot,
+                       looked);
+    const bool found = cls == 0 && b_key != kDenseEmpty;
+    const double wd = wave_sum(found ? __longlong_as_double((long long)b_bits) : 0.0);
+    const unsigned long long wl = wave_sum(looked);
+    const uint32_t n_found = (uint32_t)__popcll(__ballot(found)), n_none = (uint32_t)__popcll(__ballot(cls == 0 && !found)),
+                   n_oor = (uint32_t)__popcll(__ballot(cls == 3)), n_inv = (uint32_t)__popcll(__ballot(cls == 1));
+    if ((threadIdx.x & 63) == 0) {
+      s_d2[w] = wd;
+      s_look[w] = wl;
+      s_cnt[w][0] = n_found, s_cnt[w][1] = n_none, s_cnt[w][2] = n_oor, s_cnt[w][3] = n_inv;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      fmx_pose_score r{s_cnt[0][0], s_cnt[0][1], s_cnt[0][2], s_cnt[0][3], s_d2[0], s_look[0]};
+#pragma unroll
+      for (int i = 1; i < kScoreWaves; ++i) {  // in wave order
+        r.found += s_cnt[i][0], r.none += s_cnt[i][1], r.out_of_range += s_cnt[i][2], r.invalid += s_cnt[i][3];
+        r.sum_d2 += s_d2[i];
+        r.lookups += s_look[i];
+      }
+      part[(size_t)pose * tiles + tile] = r;
+    }
+    __syncthreads();  // (the next item writes the same words)
+  }
+}
+
+// One wave per pose of the chunk: lane l sums the partial records of tiles l, l + 64, ... in
+// that order, the wave by wave_sum's butterfly; lane 0 writes the pose's record.
+__global__ __launch_bounds__(kDenseThreads) void k_score_finish(const fmx_pose_score* __restrict__ part, uint32_t tiles,
+                                                                uint32_t poses, fmx_pose_score* __restrict__ out) {
+  const uint32_t pose = blockIdx.x * (uint32_t)kScoreWaves + threadIdx.x / kWave;  // (uniform over the wave)
+  if (pose >= poses) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  fmx_pose_score r{0u, 0u, 0u, 0u, 0.0, 0ull};
+  for (uint32_t t = lane; t < tiles; t += 64u) {
+    const fmx_pose_score q = part[(size_t)pose * tiles + t];
+    r.found += q.found, r.none += q.none, r.out_of_range += q.out_of_range, r.invalid += q.invalid;
+    r.sum_d2 += q.sum_d2;
+    r.lookups += q.lookups;
+  }
+  r.found = wave_sum(r.found), r.none = wave_sum(r.none), r.out_of_range = wave_sum(r.out_of_range),
+  r.invalid = wave_sum(r.invalid);
+  r.sum_d2 = wave_sum(r.sum_d2);
+  r.lookups = wave_sum(r.lookups);
+  if (lane == 0) out[pose] = r;
+}
+
 // ---- surface normals (DESIGN.md §Dense map, Normals; include/fmx/fmx.h, fmx_normals_build).
 // One record per table slot from the table as it stands: read only, one launch per build.
 //
@@ -1638,6 +1749,39 @@ void run_align(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const 
 void run_plane(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const double* pose34, const ProbeFilter& f,
                uint32_t reach, double max_dist2, double sigma, uint32_t seq, hipStream_t st) {
   launch_align(c, d_pts, n, every, pose34, f, reach, max_dist2, sigma, seq, st, PlaneRows{c->dense.normals.nrm.p});
+}
+
+void run_score(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, uint32_t poses, const ProbeFilter& f,
+               uint32_t reach, double max_dist2, hipStream_t st) {
+  auto& D = c->dense;
+  auto& N = D.nearest;
+  auto& S = D.score;
+  if (!N.have) {  // the cube's offsets in shell order, once per context (shared with run_nearest)
+    FMX_HIP(hipMemcpyAsync(N.offs.p, N.h_offs.data(), N.h_offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    N.have = true;
+  }
+  const double eye[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+  const DenseArgs a = dense_args(c, eye);  // (the kernel puts each item's pose in)
+  const ScorePlan plan = score_plan((unsigned long long)n, every, poses);
+  const unsigned long long items = (unsigned long long)poses * plan.tiles;  // (at most 2^24: score_plan's chunk)
+  {
+    const uint32_t blocks = (uint32_t)(items < (unsigned long long)kNearestBlocks ? items : (unsigned long long)kNearestBlocks);
+    // DESIGN.md §Dense map, Scoring: run_align's model per (pose, kept point) (the point, 16, and
+    // the own cell's key word, 8; the other lookups are not known at launch), the item's pose
+    // (96) and its partial record (32)
+    ProfScope ps(c->prof, PROF_DENSE, (double)poses * (double)plan.kept * 24.0 + (double)items * 128.0, st);
+    hipLaunchKernelGGL(k_score, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, plan.kept, every, S.poses.p, plan.tiles,
+                       (uint32_t)items, a, probe_take_args(c, f), reach, max_dist2, N.offs.p, D.keys.p, D.hits.p, D.xyz.p,
+                       S.part.p);
+    FMX_HIP(hipGetLastError());
+  }
+  {
+    // the partial records read and the poses' records written (32 each)
+    ProfScope ps(c->prof, PROF_DENSE, ((double)items + (double)poses) * 32.0, st);
+    hipLaunchKernelGGL(k_score_finish, dim3((poses + kScoreWaves - 1) / kScoreWaves), dim3(kDenseThreads), 0, st, S.part.p,
+                       plan.tiles, poses, S.out.p);
+    FMX_HIP(hipGetLastError());
+  }
 }
 
 // The build's filter; the miss array wherever it exists (the download reports misses from it).

@@ -23,6 +23,7 @@
 #include "probe_host.hpp"
 #include "nearest_host.hpp"
 #include "align_host.hpp"
+#include "score_host.hpp"
 #include "normals_host.hpp"
 #include "upload_host.hpp"
 #include "stage.hpp"
@@ -683,6 +684,14 @@ struct fmx_ctx {
       fmx::DBuf<uint32_t> ticket;
       fmx::HBuf<double> h_out;
     } align;
+    // scoring (fmx_score_poses; densemap.hip, the score block): a chunk's staged poses (12
+    // doubles each), its (pose, tile) partial records and its poses' records.  The offsets are
+    // `nearest`'s, the staged scan is `in`; nothing is shared with `align`.  Nothing here is
+    // allocated, and nothing launched, unless that entry point is called
+    struct Score {
+      fmx::DBuf<double> poses;
+      fmx::DBuf<fmx_pose_score> part, out;
+    } score;
     // surface normals (fmx_normals_*, read by fmx_plane_*; densemap.hip, the normals block):
     // one snapshot per build, exactly `slots` entries each (+ 20 B per slot): {n0, n1, n2,
     // flatness} and the support.  `current` is the one host-side flag every call that changes
@@ -1109,6 +1118,12 @@ void run_align(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const 
 // instantiation; the six counters' bits from word 32 of h_out, unoriented last)
 void run_plane(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const double* pose34, const ProbeFilter& f,
                uint32_t reach, double max_dist2, double sigma, uint32_t seq, hipStream_t st);
+// ... scoring: the records of the `poses` staged poses at c->dense.score.poses over the points
+// i % every == 0, into c->dense.score.out (two launches, queued; reads only).  The caller has
+// allocated c->dense.nearest.offs and c->dense.score's buffers (part: poses * score_plan's tiles
+// records; out: poses records); poses is at most score_plan's chunk
+void run_score(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, uint32_t poses, const ProbeFilter& f,
+               uint32_t reach, double max_dist2, hipStream_t st);
 // ... normals: one record per slot into c->dense.normals.nrm / support (exactly `slots` entries
 // each, allocated by the caller, as c->dense.nearest.offs and normals.cnt), the five counts
 // into normals.cnt, which the call zeroes first (one launch, queued; reads the table only);

@@ -205,6 +205,20 @@ class _PlaneResult(C.Structure):
                 ("counts", _PlaneCounts)]
 
 
+SCORE_MAX_POSES = 65536  # FMX_SCORE_MAX_POSES
+
+
+class _PoseScore(C.Structure):
+    _fields_ = [("found", C.c_uint32), ("none", C.c_uint32), ("out_of_range", C.c_uint32), ("invalid", C.c_uint32),
+                ("sum_d2", C.c_double), ("lookups", C.c_uint64)]
+
+
+# the same record as a numpy dtype: Context.score_poses hands the call an array of these
+SCORE_DTYPE = np.dtype([("found", np.uint32), ("none", np.uint32), ("out_of_range", np.uint32), ("invalid", np.uint32),
+                        ("sum_d2", np.float64), ("lookups", np.uint64)])
+SCORE_FIELDS = SCORE_DTYPE.names
+
+
 # FORM.dense_localize(plane=True) and FORM.dense_normals build the snapshot with these when it is
 # not current: the 3 x 3 x 3 cells around a voxel, at least 5 neighbours, l0 <= 0.1 l1
 NORMALS_DEFAULTS = dict(reach=1, max_dist=None, min_support=5, max_flatness=0.1)
@@ -280,6 +294,7 @@ EXPORTED = [
     "fmx_align_system", "fmx_align_dense",
     "fmx_normals_build", "fmx_normals_stats", "fmx_normals_download",
     "fmx_plane_system", "fmx_plane_align",
+    "fmx_score_poses", "fmx_score_plan",
 ]
 
 PAIR_SORT_FORMS = ("none", "per-block", "tail-scanned", "scatter-scanned")
@@ -297,6 +312,63 @@ def pair_sort_plan(n_planar: int, n_point: int, K: int, sorted: bool = True) -> 
     plan = {k: int(v) for k, v in zip(keys, out)}
     plan["form"] = PAIR_SORT_FORMS[plan["form"]]
     return plan
+
+
+def score_plan(n_points: int, stride: int = 1, n_poses: int = 1) -> dict:
+    """fmx_score_plan (host only, no context): the tiling and chunking of such a
+    Context.score_poses call (form_amd/csrc/score_host.hpp): kept (points), tile (points per
+    tile), tiles (per pose), chunk (poses per chunk), chunks (of this call), cap (the grid's,
+    in blocks)."""
+    out = np.zeros(6, np.uint32)
+    st = lib().fmx_score_plan(C.c_uint64(n_points), C.c_uint32(stride), C.c_uint32(n_poses), _p(out))
+    if st != FMX_OK:
+        raise FmxError(st, "fmx_score_plan")
+    return {k: int(v) for k, v in zip(("kept", "tile", "tiles", "chunk", "chunks", "cap"), out)}
+
+
+def rank_scores(scores) -> np.ndarray:
+    """The candidates of a Context.score_poses result by rank: found descending, then sum_d2
+    ascending, then the index ascending (integers and doubles compared, nothing computed;
+    score_host.hpp restates it).  Returns the indices, (K,) int64."""
+    found = np.asarray(scores["found"], np.int64)
+    d2 = np.asarray(scores["sum_d2"], np.float64)
+    return np.lexsort((np.arange(len(found)), d2, -found)).astype(np.int64)
+
+
+def pose_grid(centre34, half_xyz=(0.0, 0.0, 0.0), step_xyz=(1.0, 1.0, 1.0), half_yaw: float = 0.0,
+              step_yaw: float = 1.0) -> np.ndarray:
+    """Candidate poses on a grid around a centre pose [R_c | t_c] (3 x 4 or 4 x 4), on the
+    host: [Rz(psi) R_c | t_c + d] for psi = j * step_yaw, |j| <= floor(half_yaw / step_yaw),
+    and d_k = i_k * step_xyz[k], |i_k| <= floor(half_xyz[k] / step_xyz[k]) (a half of 0, or a
+    step that is not positive: that axis stays at the centre).  Nesting, outermost first: yaw,
+    x, y, z, each ascending; the centre is always among the candidates (every index 0).
+    Returns (K, 3, 4) float64; ValueError past SCORE_MAX_POSES."""
+    Tc = np.asarray(centre34, np.float64).reshape(-1, 4)[:3]
+
+    def steps(half, step):
+        half, step = float(half), float(step)
+        if not (half >= 0.0) or math.isinf(half):
+            raise ValueError("a half-extent must be a finite number >= 0")
+        m = int(math.floor(half / step + 1e-9)) if step > 0.0 and half > 0.0 else 0
+        return [i * step for i in range(-m, m + 1)]
+
+    yaws = steps(half_yaw, step_yaw)
+    dx, dy, dz = (steps(h, s) for h, s in zip(half_xyz, step_xyz))
+    total = len(yaws) * len(dx) * len(dy) * len(dz)
+    if total > SCORE_MAX_POSES:
+        raise ValueError(f"{total} candidates: more than SCORE_MAX_POSES ({SCORE_MAX_POSES})")
+    out = np.empty((total, 3, 4), np.float64)
+    k = 0
+    for psi in yaws:
+        c, sn = math.cos(psi), math.sin(psi)
+        Rm = np.array([[c, -sn, 0.0], [sn, c, 0.0], [0.0, 0.0, 1.0]]) @ Tc[:, :3] if psi != 0.0 else Tc[:, :3]
+        for x in dx:
+            for y in dy:
+                for z in dz:
+                    out[k, :, :3] = Rm
+                    out[k, :, 3] = Tc[:, 3] + np.array([x, y, z]) if (x, y, z) != (0.0, 0.0, 0.0) else Tc[:, 3]
+                    k += 1
+    return out
 
 
 def _p(a):
@@ -1110,6 +1182,27 @@ class Context:
         return dict(pose=out.reshape(3, 4), iters=int(res.iters), converged=bool(res.converged),
                     last_step=float(res.last_step), error=float(res.error), counts=res.counts.as_dict())
 
+    # ---------------------------------------------------------------- scoring candidate poses
+    def score_poses(self, points, poses, reach: int = 1, max_dist=None, min_hits: int = 1, max_miss_ratio=None,
+                    stride: int = 1) -> dict:
+        """fmx_score_poses: the (N, 4) float32 points (numpy, or a torch tensor on the host or
+        the device) judged at each of the K poses (K x 3 x 4, or K x 12) in one call: per pose
+        the class counts of nearest_voxels over the points i % stride == 0 (reach, max_dist,
+        min_hits, max_miss_ratio as there) and the sum of the found points' squared distances;
+        changes nothing.  Returns a dict of (K,) arrays: found, none, out_of_range, invalid
+        (uint32), sum_d2 (float64), lookups (uint64).  At most SCORE_MAX_POSES poses."""
+        prm = self._align_params(reach, max_dist, 1.0, min_hits, max_miss_ratio, stride)
+        on_dev, ptr, n, keep = _scan_ptr(points)
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        if on_dev:
+            _ready(keep)
+        rec = np.zeros(len(P), SCORE_DTYPE)
+        self._chk(self._L.fmx_score_poses(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev),
+                                          _p(P) if len(P) else None, C.c_uint32(len(P)), C.byref(prm),
+                                          _p(rec) if len(P) else None))
+        del keep
+        return {k: np.ascontiguousarray(rec[k]) for k in SCORE_FIELDS}
+
     # ---------------------------------------------------------------- surface normals of the map
     def normals_build(self, reach: int = 1, max_dist=None, min_support: int = 5, max_flatness: float = 0.1,
                       min_hits: int = 1, max_miss_ratio=None) -> dict:
@@ -1800,6 +1893,68 @@ class FORM:
         return dict(pose=got["pose"], iters=got["iters"], converged=got["converged"], n_valid=n_valid, n_found=n_found,
                     fitness=n_found / n_valid if n_valid else 0.0,
                     rmse=math.sqrt(2.0 * float(S[28]) * float(sigma) * float(sigma) / n_found) if n_found else 0.0)
+
+    def dense_score(self, points, poses, radius_m: float, stride: int = 1, min_hits: int = 1,
+                    max_miss_ratio=None) -> dict:
+        """Judge a scan at many candidate poses in one call (Context.score_poses; points as
+        dense_lookup, poses K x 3 x 4 or K x 4 x 4): per pose the counts of the radius search of
+        dense_nearest (reach from radius_m as there) over the points i % stride == 0, sum_d2,
+        and dense_fitness's figures from them: n_valid = found + none, fitness = found /
+        n_valid and rmse = sqrt(sum_d2 / found) (0.0 where the divisor is 0).  Nothing is
+        changed."""
+        P = np.asarray(poses, np.float64)
+        P = P.reshape(-1, 12) if P.ndim == 2 and P.shape[1] == 12 else P.reshape(-1, P.shape[-2], 4)[:, :3]
+        points, _ = self._probe_args(points, P[0] if len(P) else np.eye(3, 4))
+        r = float(radius_m)
+        if not (r >= 0.0) or math.isinf(r):
+            raise ValueError("radius_m must be a finite number >= 0")
+        reach = math.floor(r / float(self._dense["voxel_width"])) + 1
+        if reach > NEAREST_MAX_REACH:
+            raise ValueError(f"radius_m spans more than {NEAREST_MAX_REACH} voxels: reach {reach}")
+        got = self._est.score_poses(points, P, reach, r, min_hits, max_miss_ratio, stride)
+        found = got["found"].astype(np.float64)
+        n_valid = got["found"].astype(np.int64) + got["none"].astype(np.int64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            got["n_valid"] = n_valid
+            got["fitness"] = np.where(n_valid > 0, found / np.maximum(n_valid, 1), 0.0)
+            got["rmse"] = np.where(found > 0, np.sqrt(got["sum_d2"] / np.maximum(found, 1.0)), 0.0)
+        return got
+
+    def dense_relocalize(self, points, radius_m: float, candidates, top: int = 3, score_stride=None,
+                         plane: bool = False, **localize_kw) -> dict:
+        """Find the sensor in the dense map without a guess inside the search radius: score
+        every candidate pose (dense_score at score_stride; None: max(1, N // 4096)), rank them
+        (rank_scores), run dense_localize (radius_m, plane and localize_kw: sigma, max_iters,
+        threshold, stride, min_hits, max_miss_ratio) from each of the first `top`, and return
+        the result with the largest n_found, then the smallest rmse, then the earliest rank,
+        with candidate (its index), ranking (all indices by rank) and scores (dense_score's).
+        A candidate whose system is singular (too few found points) drops out; FmxError when
+        all of them do.  Nothing is changed, the estimator included."""
+        P = np.asarray(candidates, np.float64)
+        P = P.reshape(-1, 12) if P.ndim == 2 and P.shape[1] == 12 else P.reshape(-1, P.shape[-2], 4)[:, :3]
+        P = np.ascontiguousarray(P).reshape(-1, 3, 4)
+        if not len(P):
+            raise ValueError("no candidates")
+        n = len(points)
+        stride = max(1, n // 4096) if score_stride is None else int(score_stride)
+        scores = self.dense_score(points, P, radius_m, stride, localize_kw.get("min_hits", 1),
+                                  localize_kw.get("max_miss_ratio"))
+        ranking = rank_scores(scores)
+        best, last = None, None
+        for rank, k in enumerate(ranking[:max(int(top), 1)]):
+            try:
+                got = self.dense_localize(points, radius_m, P[k], plane=plane, **localize_kw)
+            except FmxError as e:
+                if e.status != 5:  # FMX_E_STATE: a singular system
+                    raise
+                last = e
+                continue
+            key = (-got["n_found"], got["rmse"], rank)
+            if best is None or key < best[0]:
+                best = (key, got, int(k))
+        if best is None:
+            raise last
+        return dict(best[1], candidate=best[2], ranking=ranking, scores=scores)
 
     def _need_dense(self):
         if self._est is None or self._dense is None or not self._dense["enable"]:

@@ -971,6 +971,59 @@ fmx_status fmx_plane_align(fmx_ctx* ctx, const float* xyzw, size_t n_points, int
                            const double pose_init34[12], const fmx_align_params* params, uint32_t max_iters,
                            double threshold, double pose_out34[12], fmx_plane_result* result /* may be NULL */);
 
+/* ---------------- scoring many candidate poses of a scan against the dense map ------------
+ * Where could the sensor be when no guess lies inside the search radius (a map loaded back, a
+ * lost tracker): one scan, staged once, judged at n_poses candidate poses in one call, one
+ * 32-byte record per pose and nothing per point (DESIGN.md §Dense map, Scoring;
+ * tests/score_ref.py restates it).  The call only reads: the table, the counters, the normal
+ * snapshot's `current` flag, the roll state, the spill, fmx_dense_stats, fmx_dense_last,
+ * fmx_carve_last, the estimator and fmx_current_pose are as before.
+ *   points   for every pose k independently, point i with i % stride != 0 (stride 0 reads 1) is
+ *            skipped: neither classified nor searched.  Every other point is classified and
+ *            searched exactly as fmx_nearest_voxels does it at poses34[k] (its block above:
+ *            point, filter, cube, winner), with params' min_hits, miss_num, miss_den, reach and
+ *            max_dist2 in their places there.  sigma is validated as fmx_align_system validates
+ *            it and enters nothing;
+ *   counts   found, none, out_of_range and invalid are that definition's counts, exactly; the
+ *            four sum to ceil(n_points / stride);
+ *   sum_d2   the sum of the winners' d2 over the found points, each d2 the very bit pattern
+ *            fmx_nearest_voxels would report; 0.0 exactly when found == 0;
+ *   order    the order of the sum is fixed by n_points, stride and constants of the build
+ *            alone (fmx_score_plan reports them): the kept points in tiles, a tile's waves by a
+ *            fixed butterfly and then in wave order, a pose's tiles by a fixed lane-to-tile
+ *            assignment and the same butterfly.  It does not depend on the order the threads
+ *            run in, on n_poses, or on a pose's place in the list: scores[k] is a function of
+ *            the points, the stride, the params, the map and pose k only.  A permuted pose list
+ *            gives the permuted records bit for bit, a call with that one pose the same 32
+ *            bytes, a host and a device point pointer the same bits: the call splits a long
+ *            list into chunks without anyone seeing it;
+ *   lookups  fmx_nearest_counts' diagnostic, under its bounds.
+ * The scan is staged once per call, the poses once per chunk; a chunk is two launches (the
+ * (pose, tile) partial records, then one wave per pose summing its tiles) and the records'
+ * copy out.  The call runs after whatever integration or roll is queued and returns once
+ * scores is written.  A context that never calls it allocates and launches nothing for it.
+ * Status codes: FMX_E_STATE unless the dense map is configured and enabled; FMX_E_INVAL for
+ * NULL params, NULL poses34 or scores with n_poses > 0, any non-finite pose entry (scores is
+ * untouched then), n_poses > FMX_SCORE_MAX_POSES, and every fmx_align_system case on points,
+ * n_points, reach, max_dist2 and sigma; FMX_E_OOM, nothing written, when a per-call buffer
+ * cannot be allocated.  n_poses == 0 succeeds, launches nothing and writes nothing; n_points ==
+ * 0 with n_poses > 0 succeeds, launches nothing and writes all-zero records.
+ * fmx_score_plan (host only: no context, no device, like fmx_pair_sort_plan) reports the tiling
+ * and the chunking of such a call: out = {the kept points, the points per tile, the tiles per
+ * pose, the poses per chunk (min(16384, what keeps the partial records within 32 MiB), at least
+ * 1), the chunks of this call (0 when nothing is launched), the grid's cap in blocks}.
+ * FMX_E_INVAL for NULL out, n_poses > FMX_SCORE_MAX_POSES, or n_points >= 2^32. */
+#define FMX_SCORE_MAX_POSES 65536
+typedef struct fmx_pose_score {
+  uint32_t found, none, out_of_range, invalid; /* the four sum to ceil(n_points / stride) */
+  double sum_d2;                               /* sum of the winners' d2 over the found points */
+  uint64_t lookups;                            /* diagnostic, as fmx_nearest_counts' */
+} fmx_pose_score;
+fmx_status fmx_score_poses(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                           const double* poses34 /* host, n_poses x 12 */, uint32_t n_poses,
+                           const fmx_align_params* params, fmx_pose_score* scores /* host, n_poses */);
+fmx_status fmx_score_plan(uint64_t n_points, uint32_t stride, uint32_t n_poses, uint32_t out[6]);
+
 /* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
  * pose at the middle of the last registered sweep. */
 fmx_status fmx_current_pose(fmx_ctx* ctx, double pose34[12]);
