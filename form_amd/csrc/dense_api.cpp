@@ -1,6 +1,6 @@
 // dense_api.cpp — the host layer of the dense voxel map (densemap.hip): every fmx_dense_*,
 // fmx_roll_*, fmx_carve_*, fmx_probe_*, fmx_upload_*, fmx_nearest_*, fmx_align_*, fmx_score_*,
-// fmx_normals_* and fmx_plane_* entry point of include/fmx/fmx.h, and the four calls
+// fmx_refine_*, fmx_normals_* and fmx_plane_* entry point of include/fmx/fmx.h, and the four calls
 // register_scan (fmx_api.cpp) makes into the map (fmx_api.hpp).  The argument checks that need
 // no device live in the *_host.hpp headers.
 // Host code only; built like fmx_api.cpp.
@@ -310,6 +310,56 @@ void need_normals(const fmx_ctx* c) {
   if (!c->dense.normals.current)
     throw StatusError(FMX_E_STATE, c->dense.normals.built ? "the normal snapshot is stale: the table changed since fmx_normals_build"
                                                           : "no normal snapshot (fmx_normals_build)");
+}
+
+// ---- refining (fmx_refine_systems, fmx_refine_poses; refine_host.hpp).  refine_begin: the
+// per-call buffers for the largest chunk of at most n_poses poses, every one before anything is
+// launched or written (FMX_E_OOM when one cannot be had), then the scan staged once (the caller
+// has run the checks and settled the queue).  refine_eval: the records of `count` <= n_poses
+// poses into host memory, chunk by chunk, one wait at the end; all zeros without points.
+struct RefineCall {
+  const float4* d = nullptr;
+  size_t n = 0;
+  fmx_align_params prm{};
+  bool plane = false;
+};
+RefineCall refine_begin(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, uint32_t n_poses,
+                        const fmx_align_params* prm, bool plane) {
+  auto& D = c->dense;
+  auto& Rf = D.refine;
+  RefineCall call;
+  call.n = n;
+  call.prm = *prm;
+  call.plane = plane;
+  if (!n) return call;
+  const RefinePlan plan = refine_plan((unsigned long long)n, align_stride(*prm), n_poses);
+  const uint32_t most = std::min(plan.chunk, n_poses);  // the poses of the largest chunk
+  const auto ensure = [](auto& b, size_t m) { roll_ensure(b, m, "dense map refine"); };
+  offsets_ensure(c, "dense map refine");
+  ensure(Rf.poses, (size_t)most * 12);
+  ensure(Rf.part, (size_t)most * plan.tiles);
+  ensure(Rf.out, most);
+  if (!src_on_dev) ensure(D.in, n);
+  call.d = scan_on_device(c, xyzw, n, src_on_dev);
+  return call;
+}
+void refine_eval(fmx_ctx* c, const RefineCall& call, const double* poses34, uint32_t count, fmx_refine_system* out) {
+  auto& Rf = c->dense.refine;
+  if (!call.n) {
+    std::memset(out, 0, (size_t)count * sizeof(fmx_refine_system));
+    return;
+  }
+  const uint32_t every = align_stride(call.prm);
+  const RefinePlan plan = refine_plan((unsigned long long)call.n, every, count);
+  const ProbeFilter f = probe_filter(call.prm.min_hits, call.prm.miss_num, call.prm.miss_den);
+  for (uint32_t k0 = 0; k0 < count; k0 += plan.chunk) {
+    const uint32_t k = std::min(plan.chunk, count - k0);
+    FMX_HIP(hipMemcpyAsync(Rf.poses.p, poses34 + (size_t)k0 * 12, (size_t)k * 12 * sizeof(double), hipMemcpyHostToDevice,
+                           c->stream));
+    run_refine(c, call.d, call.n, every, k, f, call.prm.reach, call.prm.max_dist2, call.prm.sigma, call.plane, c->stream);
+    FMX_HIP(hipMemcpyAsync(out + k0, Rf.out.p, (size_t)k * sizeof(fmx_refine_system), hipMemcpyDeviceToHost, c->stream));
+  }
+  FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns the points and the poses again
 }
 
 }  // namespace
@@ -886,6 +936,53 @@ fmx_status fmx_score_poses(fmx_ctx* c, const float* xyzw, size_t n, int src_on_d
 fmx_status fmx_score_plan(uint64_t n_points, uint32_t stride, uint32_t n_poses, uint32_t out[6]) {
   if (!out || n_poses > (uint32_t)FMX_SCORE_MAX_POSES || n_points >= (1ull << 32)) return FMX_E_INVAL;
   const ScorePlan p = score_plan(n_points, stride, n_poses);
+  const uint32_t v[6] = {p.kept, p.tile, p.tiles, p.chunk, p.chunks, p.cap};
+  std::memcpy(out, v, sizeof(v));
+  return FMX_OK;
+}
+
+// ---- refining many candidate poses (refine_host.hpp).  The scoring's path: the checks, the
+// queue settled, every buffer, the scan staged once (refine_begin); then per evaluation and
+// chunk the poses staged, two launches and the records' copy out, and one wait (refine_eval).
+fmx_status fmx_refine_systems(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double* poses34,
+                              uint32_t n_poses, const fmx_align_params* prm, int plane, fmx_refine_system* out) {
+  return guard<false>(c, [&] {
+    if (plane) need_normals(c);
+    else need_map(c);
+    checked([&](const char** why) {
+      return refine_check(xyzw, (unsigned long long)n, poses34, (unsigned long long)n_poses, prm, out, why);
+    });
+    dense_settle(c);
+    if (!n_poses) return;
+    const RefineCall call = refine_begin(c, xyzw, n, src_on_dev, n_poses, prm, plane != 0);
+    refine_eval(c, call, poses34, n_poses, out);
+  });
+}
+
+fmx_status fmx_refine_poses(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double* poses_init34,
+                            uint32_t n_poses, const fmx_align_params* prm, int plane, uint32_t max_iters, double threshold,
+                            double* poses_out34, fmx_refine_result* results) {
+  return guard<false>(c, [&] {
+    if (plane) need_normals(c);
+    else need_map(c);
+    checked([&](const char** why) {
+      return refine_check(xyzw, (unsigned long long)n, poses_init34, (unsigned long long)n_poses, prm, poses_out34, why);
+    });
+    checked([&](const char** why) { return refine_loop_check(threshold, why); });
+    dense_settle(c);
+    if (!n_poses) return;
+    RefineCall call;
+    if (max_iters) call = refine_begin(c, xyzw, n, src_on_dev, n_poses, prm, plane != 0);
+    refine_loop(
+        poses_init34, n_poses, max_iters, threshold,
+        [&](const double* poses, uint32_t count, fmx_refine_system* rec) { refine_eval(c, call, poses, count, rec); },
+        poses_out34, results);
+  });
+}
+
+fmx_status fmx_refine_plan(uint64_t n_points, uint32_t stride, uint32_t n_poses, uint32_t out[6]) {
+  if (!out || n_poses > (uint32_t)FMX_REFINE_MAX_POSES || n_points >= (1ull << 32)) return FMX_E_INVAL;
+  const RefinePlan p = refine_plan(n_points, stride, n_poses);
   const uint32_t v[6] = {p.kept, p.tile, p.tiles, p.chunk, p.chunks, p.cap};
   std::memcpy(out, v, sizeof(v));
   return FMX_OK;

@@ -1304,6 +1304,204 @@ __global__ __launch_bounds__(kDenseThreads) void k_score_finish(const fmx_pose_s
   if (lane == 0) out[pose] = r;
 }
 
+// ---- refining candidate poses (DESIGN.md §Dense map, Refining; include/fmx/fmx.h,
+// fmx_refine_systems).  k_align's system of one staged scan at many poses: per pose one 264-byte
+// record (the 28 sums and the error, the class counts, the lookups), nothing per point.  Read
+// only, two launches per chunk of poses on the context stream.
+//
+// k_score's item scheme with k_align's rows.  A work item is one pose and one tile of
+// kRefineTile kept points (refine_host.hpp), the items of a chunk tile-major, a block walking
+// them with a grid stride under k_nearest's cap; the item's pose comes from the staged pose
+// array, uniform over the block, into the DenseArgs that probe_classify and nearest_search<1>
+// take unchanged.  A tile is kRefineTile / 256 block-wide passes: one lane per kept point and
+// pass, the rows built exactly as k_align builds them (the same factor_rows.hpp calls with the
+// same arguments, the unoriented test on the winner's normal record included) into 28 fp64
+// accumulators that are reset per item and persist over its passes, as k_align's over its
+// trips.  Per item one reduction: the wave's reduce-scatter, then the block's waves in wave
+// order through LDS; the counts by ballots.  One partial record per item, written whole by the
+// item's block (an item that found nothing writes zeros: the finisher reads every record).
+// k_refine_finish sums a pose's tiles in an order fixed by their number, one block per pose.  Every order is fixed
+// by the kept points and the tile: which block ran an item, how many poses the chunk holds and
+// where the pose stands in it enter nothing.  The launch boundary is the hand-off: no ticket, no
+// agent-scope protocol, no floating-point atomic; nothing is shared with k_align's partials,
+// ticket and counters or with the score buffers.
+static_assert(kRefineTile % (uint32_t)kDenseThreads == 0, "a tile is a whole number of block-wide passes");
+static_assert(kRefineGridCap == (uint32_t)kNearestBlocks, "the refine grid is capped as k_nearest's");
+constexpr int kRefineWaves = kDenseThreads / kWave;
+constexpr uint32_t kRefinePasses = kRefineTile / (uint32_t)kDenseThreads;
+
+// m: the kept points; tiles = ceil(m / kRefineTile); items = poses of the chunk * tiles.
+// part[pose * tiles + tile]: written whole by the item's block.
+template <class Rows>
+__global__ __launch_bounds__(kDenseThreads) void k_refine(const float4* __restrict__ pts, uint32_t m, uint32_t every,
+                                                          const double* __restrict__ poses, uint32_t tiles, uint32_t items,
+                                                          DenseArgs a, DenseTake tk, uint32_t reach, double max_d2,
+                                                          double inv, const uint32_t* __restrict__ offs,
+                                                          const unsigned long long* __restrict__ keys,
+                                                          const uint32_t* __restrict__ hits,
+                                                          const double* __restrict__ xyz, RefinePart* __restrict__ part,
+                                                          Rows rows) {
+  constexpr bool kPlane = Rows::kCounters == 6;
+  constexpr int NG = 28;
+  __shared__ double sw[kRefineWaves][NG];
+  __shared__ unsigned long long s_look[kRefineWaves];
+  __shared__ uint32_t s_cnt[kRefineWaves][5];
+  const unsigned long long inf_bits = 0x7FF0000000000000ull;
+  const int w = threadIdx.x / kWave, lane = lane_id();
+  const uint32_t n_poses = items / tiles;
+  for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {  // (uniform over the block)
+    const uint32_t tile = item / n_poses, pose = item - tile * n_poses;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) a.T.m[k] = poses[(size_t)pose * 12 + k];
+    unsigned long long looked = 0;
+    uint32_t n_found = 0, n_none = 0, n_oor = 0, n_inv = 0, n_unor = 0;  // (the same in every lane of the wave)
+    double acc[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) acc[i] = 0.0;
+    const unsigned long long w0 = (unsigned long long)tile * kRefineTile + (threadIdx.x & ~63u);
+    for (uint32_t ps = 0; ps < kRefinePasses; ++ps) {
+      const unsigned long long off = (unsigned long long)ps * kDenseThreads;
+      if (w0 + off >= (unsigned long long)m) break;  // (uniform over the wave)
+      const unsigned long long g = w0 + off + (threadIdx.x & 63u);
+      int cls = -1;  // past the end
+      double p0 = 0.0, p1 = 0.0, p2 = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
+      int c0 = 0, c1 = 0, c2 = 0;
+      if (g < (unsigned long long)m) {
+        const float4 pf = pts[g * (unsigned long long)every];  // (g < m: the index is below n)
+        double wp[3];
+        int v[3];
+        cls = probe_classify(pf, a, wp, v);
+        p0 = wp[0], p1 = wp[1], p2 = wp[2];
+        s0 = (double)pf.x, s1 = (double)pf.y, s2 = (double)pf.z;
+        if (cls == 0) c0 = v[0], c1 = v[1], c2 = v[2];
+      }
+      unsigned long long b_bits = inf_bits, b_key = kDenseEmpty;
+      uint32_t b_slot = kDenseDropped;
+      nearest_search<1u>(cls, p0, p1, p2, c0, c1, c2, 0u, a, tk, reach, max_d2, offs, keys, hits, xyz, b_bits, b_key, b_slot,
+                         looked);
+      int st = -1;
+      if (cls >= 0) {
+        const bool found = cls == 0 && b_key != kDenseEmpty;
+        st = cls == 1 ? FMX_PROBE_INVALID : cls == 3 ? FMX_PROBE_OUT_OF_RANGE : found ? FMX_PROBE_SOLID : FMX_PROBE_ABSENT;
+        if (found) {
+          const double q[3] = {xyz[3 * (size_t)b_slot + 0], xyz[3 * (size_t)b_slot + 1], xyz[3 * (size_t)b_slot + 2]};
+          const double pj[3] = {s0, s1, s2}, wpj[3] = {p0, p1, p2};
+          double H[12];
+#pragma unroll
+          for (int i = 0; i < 12; ++i) H[i] = 0.0;
+          if constexpr (kPlane) {
+            const float4 nf = rows.nrm[b_slot];
+            if (nf.x == 0.0f && nf.y == 0.0f && nf.z == 0.0f) {
+              st = kAlignUnoriented;
+            } else {
+              const double ni[3] = {(double)nf.x, (double)nf.y, (double)nf.z};
+              const double eye[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};  // X(i)
+              double r;
+              plane_row<1>(eye, a.T.m, q, ni, pj, r, H);
+              accum_row<1>(H, r, inv, acc);
+            }
+          } else {
+#pragma unroll
+            for (int r3 = 0; r3 < 3; ++r3) {
+              double r;
+              point_row<1>(a.T.m, a.T.m, q, pj, q, wpj, r3, r, H);  // (X(i) is not read in this mode)
+              accum_row<1>(H, r, inv, acc);
+            }
+          }
+        }
+      }
+      if constexpr (kPlane) n_unor += (uint32_t)__popcll(__ballot(st == kAlignUnoriented));
+      n_found += (uint32_t)__popcll(__ballot(st == FMX_PROBE_SOLID));
+      n_none += (uint32_t)__popcll(__ballot(st == FMX_PROBE_ABSENT));
+      n_oor += (uint32_t)__popcll(__ballot(st == FMX_PROBE_OUT_OF_RANGE));
+      n_inv += (uint32_t)__popcll(__ballot(st == FMX_PROBE_INVALID));
+    }
+    const unsigned long long wl = wave_sum(looked);
+    const double mine = wave_reduce_scatter32(acc);  // entry lane / 2
+    if ((lane & 1) == 0 && (lane >> 1) < NG) sw[w][lane >> 1] = mine;
+    if (lane == 0) {
+      s_look[w] = wl;
+      s_cnt[w][0] = n_found, s_cnt[w][1] = n_none, s_cnt[w][2] = n_oor, s_cnt[w][3] = n_inv, s_cnt[w][4] = n_unor;
+    }
+    __syncthreads();
+    RefinePart* const rec = part + ((size_t)pose * tiles + tile);
+    if (threadIdx.x < NG) {
+      const int t = threadIdx.x;
+      double bp = sw[0][t];
+#pragma unroll
+      for (int i = 1; i < kRefineWaves; ++i) bp += sw[i][t];  // in wave order
+      rec->S[t] = bp;
+    } else if (threadIdx.x >= 32 && threadIdx.x < 32 + 5) {
+      const int k = threadIdx.x - 32;
+      uint32_t s = s_cnt[0][k];
+#pragma unroll
+      for (int i = 1; i < kRefineWaves; ++i) s += s_cnt[i][k];
+      rec->cnt[k] = s;
+    } else if (threadIdx.x == 32 + 5) {
+      unsigned long long s = s_look[0];
+#pragma unroll
+      for (int i = 1; i < kRefineWaves; ++i) s += s_look[i];
+      rec->reserved = 0u;
+      rec->lookups = s;
+    }
+    __syncthreads();  // (the next item writes the same words)
+  }
+}
+
+// One block per pose of the chunk.  Wave w takes the pose's tiles t = w, w + 4, ...; its lane
+// e < 28 sums entry e of their partial records in four running sums (over every fourth of
+// them) closed as (s0 + s1) + (s2 + s3), lanes 32 .. 36 the counts, lane 37 the lookups; then
+// wave 0 adds the four waves' results as (w0 + w1) + (w2 + w3) from LDS and writes the pose's
+// record.  Every order is fixed by `tiles` alone; a whole scan's thousand tiles are sixteen
+// chains of adds, not one.
+__global__ __launch_bounds__(kDenseThreads) void k_refine_finish(const RefinePart* __restrict__ part, uint32_t tiles,
+                                                                 uint32_t poses, fmx_refine_system* __restrict__ out) {
+  __shared__ double sq[kRefineWaves][28];
+  __shared__ unsigned long long sk[kRefineWaves][6];
+  static_assert(kRefineWaves == 4, "the finisher closes four waves");
+  const uint32_t pose = blockIdx.x;  // (pose < poses: the grid is the poses)
+  const uint32_t w = threadIdx.x / kWave, lane = threadIdx.x & 63u;
+  const RefinePart* const p = part + (size_t)pose * tiles;
+  if (lane < 28u) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    uint32_t t = w;
+    for (; t + 12u < tiles; t += 16u) {
+      s[0] += p[t].S[lane];
+      s[1] += p[t + 4u].S[lane];
+      s[2] += p[t + 8u].S[lane];
+      s[3] += p[t + 12u].S[lane];
+    }
+    for (int i = 0; i < 3; ++i, t += 4u)
+      if (t < tiles) s[i] += p[t].S[lane];
+    sq[w][lane] = (s[0] + s[1]) + (s[2] + s[3]);
+  } else if (lane >= 32u && lane < 37u) {
+    unsigned long long s = 0ull;
+    for (uint32_t t = w; t < tiles; t += 4u) s += p[t].cnt[lane - 32u];
+    sk[w][lane - 32u] = s;
+  } else if (lane == 37u) {
+    unsigned long long s = 0ull;
+    for (uint32_t t = w; t < tiles; t += 4u) s += p[t].lookups;
+    sk[w][5] = s;
+  }
+  __syncthreads();
+  if (w != 0u) return;
+  fmx_refine_system* const o = out + pose;
+  if (lane < 28u) {
+    const double s = (sq[0][lane] + sq[1][lane]) + (sq[2][lane] + sq[3][lane]);
+    o->S[lane] = s;
+    if (lane == 27u) o->S[28] = 0.5 * s;
+  } else if (lane >= 32u && lane < 38u) {
+    const uint32_t k = lane - 32u;
+    const unsigned long long s = (sk[0][k] + sk[1][k]) + (sk[2][k] + sk[3][k]);
+    if (k < 5u)  // found .. unoriented
+      reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(o) + offsetof(fmx_refine_system, found))[k] = (uint32_t)s;
+    else {
+      o->reserved = 0u;
+      o->lookups = s;
+    }
+  }
+}
+
 // ---- surface normals (DESIGN.md §Dense map, Normals; include/fmx/fmx.h, fmx_normals_build).
 // One record per table slot from the table as it stands: read only, one launch per build.
 //
@@ -1780,6 +1978,43 @@ void run_score(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, uint32
     ProfScope ps(c->prof, PROF_DENSE, ((double)items + (double)poses) * 32.0, st);
     hipLaunchKernelGGL(k_score_finish, dim3((poses + kScoreWaves - 1) / kScoreWaves), dim3(kDenseThreads), 0, st, S.part.p,
                        plan.tiles, poses, S.out.p);
+    FMX_HIP(hipGetLastError());
+  }
+}
+
+void run_refine(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, uint32_t poses, const ProbeFilter& f,
+                uint32_t reach, double max_dist2, double sigma, bool plane, hipStream_t st) {
+  auto& D = c->dense;
+  auto& N = D.nearest;
+  auto& Rf = D.refine;
+  if (!N.have) {  // the cube's offsets in shell order, once per context (shared with run_nearest)
+    FMX_HIP(hipMemcpyAsync(N.offs.p, N.h_offs.data(), N.h_offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    N.have = true;
+  }
+  const double eye[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+  const DenseArgs a = dense_args(c, eye);  // (the kernel puts each item's pose in)
+  const RefinePlan plan = refine_plan((unsigned long long)n, every, poses);
+  const unsigned long long items = (unsigned long long)poses * plan.tiles;  // (at most 2^22: refine_plan's chunk)
+  {
+    const uint32_t blocks = (uint32_t)(items < (unsigned long long)kNearestBlocks ? items : (unsigned long long)kNearestBlocks);
+    // DESIGN.md §Dense map, Refining: run_align's model per (pose, kept point) (the point, 16, and
+    // the own cell's key word, 8; the other lookups, and the plane form's 16 B per found point,
+    // are not known at launch), the item's pose (96) and its partial record (256)
+    ProfScope ps(c->prof, PROF_DENSE, (double)poses * (double)plan.kept * 24.0 + (double)items * 352.0, st);
+    const auto launch = [&](auto rows) {
+      hipLaunchKernelGGL(k_refine<decltype(rows)>, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, plan.kept, every,
+                         Rf.poses.p, plan.tiles, (uint32_t)items, a, probe_take_args(c, f), reach, max_dist2, 1.0 / sigma,
+                         N.offs.p, D.keys.p, D.hits.p, D.xyz.p, Rf.part.p, rows);
+    };
+    if (plane) launch(PlaneRows{D.normals.nrm.p});
+    else launch(PointRows{});
+    FMX_HIP(hipGetLastError());
+  }
+  {
+    // the partial records read (256 each) and the poses' records written (264 each)
+    ProfScope ps(c->prof, PROF_DENSE, (double)items * 256.0 + (double)poses * 264.0, st);
+    hipLaunchKernelGGL(k_refine_finish, dim3(poses), dim3(kDenseThreads), 0, st,
+                       Rf.part.p, plan.tiles, poses, Rf.out.p);
     FMX_HIP(hipGetLastError());
   }
 }

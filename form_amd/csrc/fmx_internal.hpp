@@ -23,6 +23,7 @@
 #include "probe_host.hpp"
 #include "nearest_host.hpp"
 #include "align_host.hpp"
+#include "refine_host.hpp"
 #include "score_host.hpp"
 #include "normals_host.hpp"
 #include "upload_host.hpp"
@@ -692,6 +693,16 @@ struct fmx_ctx {
       fmx::DBuf<double> poses;
       fmx::DBuf<fmx_pose_score> part, out;
     } score;
+    // refining (fmx_refine_systems, fmx_refine_poses; densemap.hip, the refine block): a chunk's
+    // staged poses (12 doubles each), its (pose, tile) partial records and its poses' records.
+    // The offsets are `nearest`'s, the staged scan is `in`; nothing is shared with `align` or
+    // `score`.  Nothing here is allocated, and nothing launched, unless one of the two entry
+    // points is called
+    struct Refine {
+      fmx::DBuf<double> poses;
+      fmx::DBuf<fmx::RefinePart> part;
+      fmx::DBuf<fmx_refine_system> out;
+    } refine;
     // surface normals (fmx_normals_*, read by fmx_plane_*; densemap.hip, the normals block):
     // one snapshot per build, exactly `slots` entries each (+ 20 B per slot): {n0, n1, n2,
     // flatness} and the support.  `current` is the one host-side flag every call that changes
@@ -1124,6 +1135,13 @@ void run_plane(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const 
 // records; out: poses records); poses is at most score_plan's chunk
 void run_score(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, uint32_t poses, const ProbeFilter& f,
                uint32_t reach, double max_dist2, hipStream_t st);
+// ... refining: the system records of the `poses` staged poses at c->dense.refine.poses over the
+// points i % every == 0, into c->dense.refine.out (two launches, queued; reads only): k_align's
+// rows, the plane form (against c->dense.normals.nrm) with `plane`.  The caller has allocated
+// c->dense.nearest.offs and c->dense.refine's buffers (part: poses * refine_plan's tiles
+// records; out: poses records); poses is at most refine_plan's chunk
+void run_refine(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, uint32_t poses, const ProbeFilter& f,
+                uint32_t reach, double max_dist2, double sigma, bool plane, hipStream_t st);
 // ... normals: one record per slot into c->dense.normals.nrm / support (exactly `slots` entries
 // each, allocated by the caller, as c->dense.nearest.offs and normals.cnt), the five counts
 // into normals.cnt, which the call zeroes first (one launch, queued; reads the table only);

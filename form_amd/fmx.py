@@ -219,6 +219,34 @@ SCORE_DTYPE = np.dtype([("found", np.uint32), ("none", np.uint32), ("out_of_rang
 SCORE_FIELDS = SCORE_DTYPE.names
 
 
+REFINE_MAX_POSES = 65536  # FMX_REFINE_MAX_POSES
+
+
+class _RefineSystem(C.Structure):
+    _fields_ = [("S", C.c_double * 29), ("found", C.c_uint32), ("none", C.c_uint32), ("out_of_range", C.c_uint32),
+                ("invalid", C.c_uint32), ("unoriented", C.c_uint32), ("reserved", C.c_uint32), ("lookups", C.c_uint64)]
+
+
+class _RefineResult(C.Structure):
+    _fields_ = [("iters", C.c_uint32), ("converged", C.c_int32), ("singular", C.c_int32), ("reserved", C.c_uint32),
+                ("last_step", C.c_double), ("error", C.c_double), ("found", C.c_uint32), ("none", C.c_uint32),
+                ("out_of_range", C.c_uint32), ("invalid", C.c_uint32), ("unoriented", C.c_uint32),
+                ("reserved2", C.c_uint32), ("lookups", C.c_uint64)]
+
+
+# the same records as numpy dtypes: Context.refine_systems / refine_poses hand the calls arrays of these
+REFINE_SYSTEM_DTYPE = np.dtype([("system", np.float64, (29,)), ("found", np.uint32), ("none", np.uint32),
+                                ("out_of_range", np.uint32), ("invalid", np.uint32), ("unoriented", np.uint32),
+                                ("reserved", np.uint32), ("lookups", np.uint64)])
+REFINE_RESULT_DTYPE = np.dtype([("iters", np.uint32), ("converged", np.int32), ("singular", np.int32),
+                                ("reserved", np.uint32), ("last_step", np.float64), ("error", np.float64),
+                                ("found", np.uint32), ("none", np.uint32), ("out_of_range", np.uint32),
+                                ("invalid", np.uint32), ("unoriented", np.uint32), ("reserved2", np.uint32),
+                                ("lookups", np.uint64)])
+REFINE_SYSTEM_FIELDS = tuple(k for k in REFINE_SYSTEM_DTYPE.names if k != "reserved")
+REFINE_RESULT_FIELDS = tuple(k for k in REFINE_RESULT_DTYPE.names if not k.startswith("reserved"))
+
+
 # FORM.dense_localize(plane=True) and FORM.dense_normals build the snapshot with these when it is
 # not current: the 3 x 3 x 3 cells around a voxel, at least 5 neighbours, l0 <= 0.1 l1
 NORMALS_DEFAULTS = dict(reach=1, max_dist=None, min_support=5, max_flatness=0.1)
@@ -295,6 +323,7 @@ EXPORTED = [
     "fmx_normals_build", "fmx_normals_stats", "fmx_normals_download",
     "fmx_plane_system", "fmx_plane_align",
     "fmx_score_poses", "fmx_score_plan",
+    "fmx_refine_systems", "fmx_refine_poses", "fmx_refine_plan",
 ]
 
 PAIR_SORT_FORMS = ("none", "per-block", "tail-scanned", "scatter-scanned")
@@ -323,6 +352,16 @@ def score_plan(n_points: int, stride: int = 1, n_poses: int = 1) -> dict:
     st = lib().fmx_score_plan(C.c_uint64(n_points), C.c_uint32(stride), C.c_uint32(n_poses), _p(out))
     if st != FMX_OK:
         raise FmxError(st, "fmx_score_plan")
+    return {k: int(v) for k, v in zip(("kept", "tile", "tiles", "chunk", "chunks", "cap"), out)}
+
+
+def refine_plan(n_points: int, stride: int = 1, n_poses: int = 1) -> dict:
+    """fmx_refine_plan (host only, no context): the tiling and chunking of such a
+    Context.refine_systems call (form_amd/csrc/refine_host.hpp), score_plan's six figures."""
+    out = np.zeros(6, np.uint32)
+    st = lib().fmx_refine_plan(C.c_uint64(n_points), C.c_uint32(stride), C.c_uint32(n_poses), _p(out))
+    if st != FMX_OK:
+        raise FmxError(st, "fmx_refine_plan")
     return {k: int(v) for k, v in zip(("kept", "tile", "tiles", "chunk", "chunks", "cap"), out)}
 
 
@@ -1203,6 +1242,50 @@ class Context:
         del keep
         return {k: np.ascontiguousarray(rec[k]) for k in SCORE_FIELDS}
 
+    # ---------------------------------------------------------------- refining candidate poses
+    def refine_systems(self, points, poses, reach: int = 1, max_dist=None, sigma: float = 1.0, min_hits: int = 1,
+                       max_miss_ratio=None, stride: int = 1, plane: bool = False) -> dict:
+        """fmx_refine_systems: align_system's (plane=True: plane_system's) system of the (N, 4)
+        float32 points at each of the K poses (K x 3 x 4, or K x 12) in one call; arguments as
+        align_system; changes nothing.  Returns a dict of arrays: system (K, 29) float64, found,
+        none, out_of_range, invalid, unoriented (uint32, unoriented 0 unless plane), lookups
+        (uint64).  At most REFINE_MAX_POSES poses."""
+        prm = self._align_params(reach, max_dist, sigma, min_hits, max_miss_ratio, stride)
+        on_dev, ptr, n, keep = _scan_ptr(points)
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        if on_dev:
+            _ready(keep)
+        rec = np.zeros(len(P), REFINE_SYSTEM_DTYPE)
+        self._chk(self._L.fmx_refine_systems(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev),
+                                             _p(P) if len(P) else None, C.c_uint32(len(P)), C.byref(prm),
+                                             C.c_int(int(bool(plane))), _p(rec) if len(P) else None))
+        del keep
+        return {k: np.ascontiguousarray(rec[k]) for k in REFINE_SYSTEM_FIELDS}
+
+    def refine_poses(self, points, poses_init, reach: int = 1, max_dist=None, sigma: float = 1.0, min_hits: int = 1,
+                     max_miss_ratio=None, stride: int = 1, max_iters: int = 30, threshold: float = 1e-6,
+                     plane: bool = False) -> dict:
+        """fmx_refine_poses: dense_align's loop from each of the K poses_init at once, all poses
+        that are still running evaluated together per iteration (arguments as dense_align);
+        changes nothing.  Returns a dict of arrays: pose (K, 3, 4), iters, converged, singular
+        (bool; such a pose is returned as it came), last_step, error and the last system's
+        found, none, out_of_range, invalid, unoriented and lookups."""
+        prm = self._align_params(reach, max_dist, sigma, min_hits, max_miss_ratio, stride)
+        on_dev, ptr, n, keep = _scan_ptr(points)
+        P = np.ascontiguousarray(poses_init, np.float64).reshape(-1, 12)
+        if on_dev:
+            _ready(keep)
+        out = np.zeros((len(P), 12), np.float64)
+        res = np.zeros(len(P), REFINE_RESULT_DTYPE)
+        self._chk(self._L.fmx_refine_poses(self.h, ptr if n else None, C.c_size_t(n), C.c_int(on_dev),
+                                           _p(P) if len(P) else None, C.c_uint32(len(P)), C.byref(prm),
+                                           C.c_int(int(bool(plane))), C.c_uint32(max_iters), C.c_double(threshold),
+                                           _p(out) if len(P) else None, _p(res) if len(P) else None))
+        del keep
+        got = {k: np.ascontiguousarray(res[k]) for k in REFINE_RESULT_FIELDS}
+        got["converged"], got["singular"] = got["converged"] != 0, got["singular"] != 0
+        return dict(got, pose=out.reshape(-1, 3, 4))
+
     # ---------------------------------------------------------------- surface normals of the map
     def normals_build(self, reach: int = 1, max_dist=None, min_support: int = 5, max_flatness: float = 0.1,
                       min_hits: int = 1, max_miss_ratio=None) -> dict:
@@ -1894,6 +1977,42 @@ class FORM:
                     fitness=n_found / n_valid if n_valid else 0.0,
                     rmse=math.sqrt(2.0 * float(S[28]) * float(sigma) * float(sigma) / n_found) if n_found else 0.0)
 
+    def dense_localize_many(self, points, radius_m: float, pose_guesses, sigma: float = 0.1, max_iters: int = 30,
+                            threshold: float = 1e-6, stride: int = 1, min_hits: int = 1, max_miss_ratio=None,
+                            plane: bool = False) -> dict:
+        """dense_localize from K guesses at once (Context.refine_poses; pose_guesses K x 3 x 4,
+        K x 4 x 4 or K x 12, the other arguments as dense_localize): the batched Gauss-Newton
+        loop, then one more batched system evaluation at the final poses.  Returns a dict of
+        (K, ...) arrays: pose, iters, converged, singular (such a guess is reported, not
+        raised, and its pose is the guess) and, by dense_localize's formulas from that
+        evaluation, n_valid, n_found, fitness, rmse (and n_unoriented with plane=True).  Nothing
+        is changed, the estimator included."""
+        P = np.asarray(pose_guesses, np.float64)
+        P = P.reshape(-1, 12) if P.ndim == 2 and P.shape[1] == 12 else P.reshape(-1, P.shape[-2], 4)[:, :3]
+        P = np.ascontiguousarray(P).reshape(-1, 12)
+        points, _ = self._probe_args(points, P[0].reshape(3, 4) if len(P) else np.eye(3, 4))
+        r = float(radius_m)
+        if not (r >= 0.0) or math.isinf(r):
+            raise ValueError("radius_m must be a finite number >= 0")
+        reach = math.floor(r / float(self._dense["voxel_width"])) + 1
+        if reach > NEAREST_MAX_REACH:
+            raise ValueError(f"radius_m spans more than {NEAREST_MAX_REACH} voxels: reach {reach}")
+        if plane and not self._est.normals_stats()["current"]:
+            self._est.normals_build(min_hits=min_hits, max_miss_ratio=max_miss_ratio, **NORMALS_DEFAULTS)
+        got = self._est.refine_poses(points, P, reach, r, sigma, min_hits, max_miss_ratio, stride, max_iters, threshold, plane)
+        last = self._est.refine_systems(points, got["pose"], reach, r, sigma, min_hits, max_miss_ratio, stride, plane)
+        n_found = last["found"].astype(np.int64)
+        n_valid = n_found + last["none"].astype(np.int64) + last["unoriented"].astype(np.int64)
+        s2 = float(sigma) * float(sigma)
+        fitness = np.array([int(f) / int(v) if v else 0.0 for f, v in zip(n_found, n_valid)], np.float64)
+        rmse = np.array([math.sqrt(2.0 * float(e) * s2 / int(f)) if f else 0.0 for e, f in zip(last["system"][:, 28], n_found)],
+                        np.float64)
+        out = dict(pose=got["pose"], iters=got["iters"], converged=got["converged"], singular=got["singular"],
+                   n_valid=n_valid, n_found=n_found, fitness=fitness, rmse=rmse)
+        if plane:
+            out["n_unoriented"] = last["unoriented"].astype(np.int64)
+        return out
+
     def dense_score(self, points, poses, radius_m: float, stride: int = 1, min_hits: int = 1,
                     max_miss_ratio=None) -> dict:
         """Judge a scan at many candidate poses in one call (Context.score_poses; points as
@@ -1921,7 +2040,7 @@ class FORM:
         return got
 
     def dense_relocalize(self, points, radius_m: float, candidates, top: int = 3, score_stride=None,
-                         plane: bool = False, **localize_kw) -> dict:
+                         plane: bool = False, batched: bool = False, **localize_kw) -> dict:
         """Find the sensor in the dense map without a guess inside the search radius: score
         every candidate pose (dense_score at score_stride; None: max(1, N // 4096)), rank them
         (rank_scores), run dense_localize (radius_m, plane and localize_kw: sigma, max_iters,
@@ -1929,7 +2048,10 @@ class FORM:
         the result with the largest n_found, then the smallest rmse, then the earliest rank,
         with candidate (its index), ranking (all indices by rank) and scores (dense_score's).
         A candidate whose system is singular (too few found points) drops out; FmxError when
-        all of them do.  Nothing is changed, the estimator included."""
+        all of them do.  Nothing is changed, the estimator included.
+        batched=True refines the first `top` in one dense_localize_many call instead (one pair
+        of launches per iteration however many are still running) and picks by the same rule;
+        the result's entries are those of dense_localize, from that call."""
         P = np.asarray(candidates, np.float64)
         P = P.reshape(-1, 12) if P.ndim == 2 and P.shape[1] == 12 else P.reshape(-1, P.shape[-2], 4)[:, :3]
         P = np.ascontiguousarray(P).reshape(-1, 3, 4)
@@ -1940,6 +2062,25 @@ class FORM:
         scores = self.dense_score(points, P, radius_m, stride, localize_kw.get("min_hits", 1),
                                   localize_kw.get("max_miss_ratio"))
         ranking = rank_scores(scores)
+        if batched:
+            first = ranking[:max(int(top), 1)]
+            many = self.dense_localize_many(points, radius_m, P[first], plane=plane, **localize_kw)
+            best = None
+            for rank, k in enumerate(first):
+                if many["singular"][rank]:
+                    continue
+                key = (-int(many["n_found"][rank]), float(many["rmse"][rank]), rank)
+                if best is None or key < best[0]:
+                    best = (key, rank, int(k))
+            if best is None:
+                raise FmxError(5, "dense_relocalize: every candidate's system is singular (too few found points)")
+            j = best[1]
+            got = dict(pose=many["pose"][j].copy(), iters=int(many["iters"][j]), converged=bool(many["converged"][j]),
+                       n_valid=int(many["n_valid"][j]), n_found=int(many["n_found"][j]))
+            if plane:
+                got["n_unoriented"] = int(many["n_unoriented"][j])
+            got.update(fitness=float(many["fitness"][j]), rmse=float(many["rmse"][j]))
+            return dict(got, candidate=best[2], ranking=ranking, scores=scores)
         best, last = None, None
         for rank, k in enumerate(ranking[:max(int(top), 1)]):
             try:

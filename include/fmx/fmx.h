@@ -1024,6 +1024,90 @@ fmx_status fmx_score_poses(fmx_ctx* ctx, const float* xyzw, size_t n_points, int
                            const fmx_align_params* params, fmx_pose_score* scores /* host, n_poses */);
 fmx_status fmx_score_plan(uint64_t n_points, uint32_t stride, uint32_t n_poses, uint32_t out[6]);
 
+/* ---------------- refining many candidate poses at once: batched alignment systems --------
+ * The batched form of the alignment itself: the 7 x 7 Gauss-Newton system of one staged scan at
+ * n_poses poses in one call, point-to-point (plane == 0: fmx_align_system's) or point-to-plane
+ * (plane != 0: fmx_plane_system's), one 264-byte record per pose and nothing per point, and on
+ * top of it a Gauss-Newton loop that advances all poses in lockstep (DESIGN.md §Dense map,
+ * Refining; tests/refine_ref.py restates it).  Both calls only read: the table, the counters,
+ * the normal snapshot's `current` flag, the roll state, the spill, fmx_dense_stats,
+ * fmx_dense_last, fmx_carve_last, the estimator and fmx_current_pose are as before.
+ * fmx_refine_systems:
+ *   points   for every pose k independently, the points with i % stride == 0 (stride 0 reads 1)
+ *            are classified and searched exactly as fmx_align_system, or with plane != 0
+ *            fmx_plane_system, does it at poses34[k], and each found point contributes the very rows
+ *            it contributes there: every per-point term has the same bits;
+ *   counts   found, none, out_of_range, invalid and, in the plane form, unoriented (0 in the
+ *            point form) are that definition's counts, exactly; they sum to ceil(n_points /
+ *            stride).  `skipped` is the same for every pose and is not repeated per record;
+ *            reserved is 0; lookups is fmx_nearest_counts' diagnostic;
+ *   S        S[0..27] is the packed upper 7 x 7 of the sum of the rows' v v^T and S[28] =
+ *            0.5 * S[27], as fmx_align_system's out.  A pose at which nothing is found has S
+ *            all +0.0;
+ *   order    the order of each of the 28 sums is fixed by n_points, stride and constants of the
+ *            build alone (fmx_refine_plan reports them): a lane's kept points of a tile in
+ *            index order, a wave by a fixed reduce-scatter, a tile's waves in wave order, a
+ *            pose's tiles in an order fixed by their number.  It does not depend on the order the threads run in, on
+ *            n_poses, or on a pose's place in the list: out[k] is a function of the points, the
+ *            stride, the params, plane, the map (and the normal snapshot) and pose k only.  A
+ *            permuted pose list gives the permuted records byte for byte, a call with that one
+ *            pose the same 264 bytes, a host and a device point pointer the same bytes: the
+ *            call splits a long list into chunks without anyone seeing it.  The order is not
+ *            fmx_align_system's, whose order depends on its launch grid: against that call at
+ *            the same pose the sums agree to rounding, not bit for bit; the counts and lookups
+ *            are equal.
+ * fmx_refine_poses runs fmx_align_dense's recurrence for every pose k on its own records.  From
+ * T = poses_init34[k], while iters < max_iters: take its system at T (++iters), solve H dx = g
+ * by Cholesky, T = T * Exp(dx), stop once ||dx|| < threshold.  All poses that are still running
+ * are evaluated together, one batched evaluation per round, in list order; because a record
+ * depends on its own pose alone, poses_out34[k] and results[k] are byte for byte what a call
+ * with that one pose returns.  A pose whose system is singular (too few found points) leaves the
+ * loop with singular = 1 and converged = 0, its iters counting the singular evaluation, error
+ * and the counts those of the singular system, last_step that of the last step it took (0 when
+ * it took none), and poses_out34[k] = poses_init34[k] bit for bit; the call still returns
+ * FMX_OK: one bad candidate does not fail the others.  max_iters == 0 returns the initial poses
+ * with iters = 0.  The scan is staged once per call; a round stages the active poses, runs two
+ * launches per chunk (the (pose, tile) partial records, then one block per pose summing its
+ * tiles), copies the records out and waits once; the 6 x 6 solves are the host's.
+ * Status codes: FMX_E_STATE unless the dense map is configured and enabled, and, with plane !=
+ * 0, unless the normal snapshot is current; FMX_E_INVAL, the outputs untouched, for NULL params,
+ * NULL poses or outputs (results may be NULL) with n_poses > 0, any non-finite pose entry,
+ * n_poses > FMX_REFINE_MAX_POSES, every fmx_align_system case on points, n_points, reach,
+ * max_dist2 and sigma, and for the loop a NaN or negative threshold; FMX_E_OOM, nothing
+ * written, when a per-call buffer cannot be had.  n_poses == 0 succeeds and writes nothing;
+ * n_points == 0 with n_poses > 0 succeeds, launches nothing and writes all-zero systems (in the
+ * loop every pose is then singular at iteration 1).  A context that never calls these
+ * functions allocates and launches nothing for them.
+ * fmx_refine_plan (host only: no context, no device, like fmx_score_plan) reports the tiling
+ * and the chunking of such a call: out = {the kept points, the kept points per tile, the tiles
+ * per pose, the poses per chunk (min(16384, what keeps the partial records within 32 MiB), at
+ * least 1), the chunks of this call (0 when nothing is launched), the grid's cap in blocks}.
+ * FMX_E_INVAL for NULL out, n_poses > FMX_REFINE_MAX_POSES, or n_points >= 2^32. */
+#define FMX_REFINE_MAX_POSES 65536
+typedef struct fmx_refine_system { /* 264 bytes */
+  double S[29];                    /* packed upper 7 x 7 and the error, as fmx_align_system's out */
+  uint32_t found, none, out_of_range, invalid, unoriented, reserved; /* they sum to ceil(n_points / stride) */
+  uint64_t lookups;                /* diagnostic, as fmx_nearest_counts' */
+} fmx_refine_system;
+fmx_status fmx_refine_systems(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                              const double* poses34 /* host, n_poses x 12 */, uint32_t n_poses,
+                              const fmx_align_params* params, int plane, fmx_refine_system* out /* host, n_poses */);
+typedef struct fmx_refine_result {
+  uint32_t iters;     /* systems evaluated */
+  int32_t converged;  /* 1 iff the last step's norm < threshold */
+  int32_t singular;   /* 1 iff the loop ended on a singular system */
+  uint32_t reserved;  /* 0 */
+  double last_step;   /* ||dx|| of the last step taken, 0 when none was */
+  double error;       /* S[28] of the last system evaluated */
+  uint32_t found, none, out_of_range, invalid, unoriented, reserved2; /* of the last system evaluated */
+  uint64_t lookups;
+} fmx_refine_result;
+fmx_status fmx_refine_poses(fmx_ctx* ctx, const float* xyzw, size_t n_points, int src_on_device,
+                            const double* poses_init34 /* host, n_poses x 12 */, uint32_t n_poses,
+                            const fmx_align_params* params, int plane, uint32_t max_iters, double threshold,
+                            double* poses_out34 /* host, n_poses x 12 */, fmx_refine_result* results /* may be NULL */);
+fmx_status fmx_refine_plan(uint64_t n_points, uint32_t stride, uint32_t n_poses, uint32_t out[6]);
+
 /* Estimator::current_lidar_estimate (form/form.hpp:79).  With deskewing on: the sensor
  * pose at the middle of the last registered sweep. */
 fmx_status fmx_current_pose(fmx_ctx* ctx, double pose34[12]);
