@@ -312,54 +312,68 @@ void need_normals(const fmx_ctx* c) {
                                                           : "no normal snapshot (fmx_normals_build)");
 }
 
-// ---- refining (fmx_refine_systems, fmx_refine_poses; refine_host.hpp).  refine_begin: the
-// per-call buffers for the largest chunk of at most n_poses poses, every one before anything is
-// launched or written (FMX_E_OOM when one cannot be had), then the scan staged once (the caller
-// has run the checks and settled the queue).  refine_eval: the records of `count` <= n_poses
-// poses into host memory, chunk by chunk, one wait at the end; all zeros without points.
-struct RefineCall {
+// ---- pose batches (fmx_score_poses, fmx_refine_systems, fmx_refine_poses; score_host.hpp,
+// refine_host.hpp), the caller having run the checks and settled the queue.  pose_batch_begin:
+// the buffers `buf` of the feature `what` for the largest chunk of at most n_poses poses, every
+// one before anything is launched or written (FMX_E_OOM when one cannot be had), then the scan
+// staged once; nothing without points.  pose_batch_eval: the records of `count` <= n_poses poses
+// into host memory, chunk by chunk (the poses staged, run(k) queueing the two launches over
+// them, the records' copy out), one wait at the end; all zeros without points.
+struct PoseBatchCall {
   const float4* d = nullptr;
   size_t n = 0;
   fmx_align_params prm{};
   bool plane = false;
+  uint32_t every = 1, chunk = 1;
+  ProbeFilter f{};
 };
-RefineCall refine_begin(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, uint32_t n_poses,
-                        const fmx_align_params* prm, bool plane) {
-  auto& D = c->dense;
-  auto& Rf = D.refine;
-  RefineCall call;
-  call.n = n;
-  call.prm = *prm;
-  call.plane = plane;
+template <class B>
+PoseBatchCall pose_batch_begin(fmx_ctx* c, B& buf, const char* what, const BatchPlan& plan, const float* xyzw, size_t n,
+                               int src_on_dev, uint32_t n_poses, const fmx_align_params* prm, bool plane) {
+  PoseBatchCall call{nullptr, n, *prm, plane, align_stride(*prm), plan.chunk,
+                     probe_filter(prm->min_hits, prm->miss_num, prm->miss_den)};
   if (!n) return call;
-  const RefinePlan plan = refine_plan((unsigned long long)n, align_stride(*prm), n_poses);
   const uint32_t most = std::min(plan.chunk, n_poses);  // the poses of the largest chunk
-  const auto ensure = [](auto& b, size_t m) { roll_ensure(b, m, "dense map refine"); };
-  offsets_ensure(c, "dense map refine");
-  ensure(Rf.poses, (size_t)most * 12);
-  ensure(Rf.part, (size_t)most * plan.tiles);
-  ensure(Rf.out, most);
-  if (!src_on_dev) ensure(D.in, n);
+  const auto ensure = [&](auto& b, size_t m) { roll_ensure(b, m, what); };
+  offsets_ensure(c, what);
+  ensure(buf.poses, (size_t)most * 12);
+  ensure(buf.part, (size_t)most * plan.tiles);
+  ensure(buf.out, most);
+  if (!src_on_dev) ensure(c->dense.in, n);
   call.d = scan_on_device(c, xyzw, n, src_on_dev);
   return call;
 }
-void refine_eval(fmx_ctx* c, const RefineCall& call, const double* poses34, uint32_t count, fmx_refine_system* out) {
-  auto& Rf = c->dense.refine;
+template <class B, class Rec, class Run>
+void pose_batch_eval(fmx_ctx* c, B& buf, const PoseBatchCall& call, const double* poses34, uint32_t count, Rec* out, Run&& run) {
   if (!call.n) {
-    std::memset(out, 0, (size_t)count * sizeof(fmx_refine_system));
+    std::memset(out, 0, (size_t)count * sizeof(Rec));
     return;
   }
-  const uint32_t every = align_stride(call.prm);
-  const RefinePlan plan = refine_plan((unsigned long long)call.n, every, count);
-  const ProbeFilter f = probe_filter(call.prm.min_hits, call.prm.miss_num, call.prm.miss_den);
-  for (uint32_t k0 = 0; k0 < count; k0 += plan.chunk) {
-    const uint32_t k = std::min(plan.chunk, count - k0);
-    FMX_HIP(hipMemcpyAsync(Rf.poses.p, poses34 + (size_t)k0 * 12, (size_t)k * 12 * sizeof(double), hipMemcpyHostToDevice,
+  for (uint32_t k0 = 0; k0 < count; k0 += call.chunk) {
+    const uint32_t k = std::min(call.chunk, count - k0);
+    FMX_HIP(hipMemcpyAsync(buf.poses.p, poses34 + (size_t)k0 * 12, (size_t)k * 12 * sizeof(double), hipMemcpyHostToDevice,
                            c->stream));
-    run_refine(c, call.d, call.n, every, k, f, call.prm.reach, call.prm.max_dist2, call.prm.sigma, call.plane, c->stream);
-    FMX_HIP(hipMemcpyAsync(out + k0, Rf.out.p, (size_t)k * sizeof(fmx_refine_system), hipMemcpyDeviceToHost, c->stream));
+    run(k);
+    FMX_HIP(hipMemcpyAsync(out + k0, buf.out.p, (size_t)k * sizeof(Rec), hipMemcpyDeviceToHost, c->stream));
   }
   FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns the points and the poses again
+}
+// fmx_score_plan's and fmx_refine_plan's body.
+fmx_status plan_export(const BatchPlan& p, uint32_t out[6]) {
+  const uint32_t v[6] = {p.kept, p.tile, p.tiles, p.chunk, p.chunks, p.cap};
+  std::memcpy(out, v, sizeof(v));
+  return FMX_OK;
+}
+
+PoseBatchCall refine_begin(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, uint32_t n_poses,
+                           const fmx_align_params* prm, bool plane) {
+  return pose_batch_begin(c, c->dense.refine, "dense map refine", refine_plan((unsigned long long)n, prm->stride, n_poses), xyzw, n,
+                          src_on_dev, n_poses, prm, plane);
+}
+void refine_eval(fmx_ctx* c, const PoseBatchCall& call, const double* poses34, uint32_t count, fmx_refine_system* out) {
+  pose_batch_eval(c, c->dense.refine, call, poses34, count, out, [&](uint32_t k) {
+    run_refine(c, call.d, call.n, call.every, k, call.f, call.prm.reach, call.prm.max_dist2, call.prm.sigma, call.plane, c->stream);
+  });
 }
 
 }  // namespace
@@ -893,57 +907,33 @@ fmx_status fmx_align_dense(fmx_ctx* c, const float* xyzw, size_t n, int src_on_d
 }
 
 // ---- scoring many candidate poses (score_host.hpp).  The queries' path: the checks, the queue
-// settled, every buffer, the scan staged once; then per chunk the poses staged, two launches and
-// the records' copy out, and one wait at the end.
+// settled, then pose_batch_begin and one pose_batch_eval.
 fmx_status fmx_score_poses(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double* poses34,
                            uint32_t n_poses, const fmx_align_params* prm, fmx_pose_score* scores) {
   return guard<false>(c, [&] {
     auto& D = c->dense;
-    auto& S = D.score;
     need_map(c);
     checked([&](const char** why) {
       return score_check(xyzw, (unsigned long long)n, poses34, (unsigned long long)n_poses, prm, scores, why);
     });
     dense_settle(c);
     if (!n_poses) return;
-    if (!n) {
-      std::memset(scores, 0, (size_t)n_poses * sizeof(fmx_pose_score));
-      return;
-    }
-    const uint32_t every = align_stride(*prm);
-    const ScorePlan plan = score_plan((unsigned long long)n, every, n_poses);
-    const uint32_t most = std::min(plan.chunk, n_poses);  // the poses of the largest chunk
-    // every buffer before anything is launched or written (FMX_E_OOM when one cannot be had)
-    const auto ensure = [](auto& b, size_t m) { roll_ensure(b, m, "dense map score"); };
-    offsets_ensure(c, "dense map score");
-    ensure(S.poses, (size_t)most * 12);
-    ensure(S.part, (size_t)most * plan.tiles);
-    ensure(S.out, most);
-    if (!src_on_dev) ensure(D.in, n);
-    const float4* d = scan_on_device(c, xyzw, n, src_on_dev);
-    const ProbeFilter f = probe_filter(prm->min_hits, prm->miss_num, prm->miss_den);
-    for (uint32_t k0 = 0; k0 < n_poses; k0 += plan.chunk) {
-      const uint32_t k = std::min(plan.chunk, n_poses - k0);
-      FMX_HIP(hipMemcpyAsync(S.poses.p, poses34 + (size_t)k0 * 12, (size_t)k * 12 * sizeof(double), hipMemcpyHostToDevice,
-                             c->stream));
-      run_score(c, d, n, every, k, f, prm->reach, prm->max_dist2, c->stream);
-      FMX_HIP(hipMemcpyAsync(scores + k0, S.out.p, (size_t)k * sizeof(fmx_pose_score), hipMemcpyDeviceToHost, c->stream));
-    }
-    FMX_HIP(hipStreamSynchronize(c->stream));  // the caller owns the points and the poses again
+    const PoseBatchCall call = pose_batch_begin(c, D.score, "dense map score", score_plan((unsigned long long)n, prm->stride, n_poses),
+                                                xyzw, n, src_on_dev, n_poses, prm, false);
+    pose_batch_eval(c, D.score, call, poses34, n_poses, scores, [&](uint32_t k) {
+      run_score(c, call.d, n, call.every, k, call.f, prm->reach, prm->max_dist2, c->stream);
+    });
   });
 }
 
 fmx_status fmx_score_plan(uint64_t n_points, uint32_t stride, uint32_t n_poses, uint32_t out[6]) {
   if (!out || n_poses > (uint32_t)FMX_SCORE_MAX_POSES || n_points >= (1ull << 32)) return FMX_E_INVAL;
-  const ScorePlan p = score_plan(n_points, stride, n_poses);
-  const uint32_t v[6] = {p.kept, p.tile, p.tiles, p.chunk, p.chunks, p.cap};
-  std::memcpy(out, v, sizeof(v));
-  return FMX_OK;
+  return plan_export(score_plan(n_points, stride, n_poses), out);
 }
 
 // ---- refining many candidate poses (refine_host.hpp).  The scoring's path: the checks, the
-// queue settled, every buffer, the scan staged once (refine_begin); then per evaluation and
-// chunk the poses staged, two launches and the records' copy out, and one wait (refine_eval).
+// queue settled, pose_batch_begin (refine_begin), then one pose_batch_eval per evaluation
+// (refine_eval).
 fmx_status fmx_refine_systems(fmx_ctx* c, const float* xyzw, size_t n, int src_on_dev, const double* poses34,
                               uint32_t n_poses, const fmx_align_params* prm, int plane, fmx_refine_system* out) {
   return guard<false>(c, [&] {
@@ -954,7 +944,7 @@ fmx_status fmx_refine_systems(fmx_ctx* c, const float* xyzw, size_t n, int src_o
     });
     dense_settle(c);
     if (!n_poses) return;
-    const RefineCall call = refine_begin(c, xyzw, n, src_on_dev, n_poses, prm, plane != 0);
+    const PoseBatchCall call = refine_begin(c, xyzw, n, src_on_dev, n_poses, prm, plane != 0);
     refine_eval(c, call, poses34, n_poses, out);
   });
 }
@@ -971,7 +961,7 @@ fmx_status fmx_refine_poses(fmx_ctx* c, const float* xyzw, size_t n, int src_on_
     checked([&](const char** why) { return refine_loop_check(threshold, why); });
     dense_settle(c);
     if (!n_poses) return;
-    RefineCall call;
+    PoseBatchCall call;
     if (max_iters) call = refine_begin(c, xyzw, n, src_on_dev, n_poses, prm, plane != 0);
     refine_loop(
         poses_init34, n_poses, max_iters, threshold,
@@ -982,10 +972,7 @@ fmx_status fmx_refine_poses(fmx_ctx* c, const float* xyzw, size_t n, int src_on_
 
 fmx_status fmx_refine_plan(uint64_t n_points, uint32_t stride, uint32_t n_poses, uint32_t out[6]) {
   if (!out || n_poses > (uint32_t)FMX_REFINE_MAX_POSES || n_points >= (1ull << 32)) return FMX_E_INVAL;
-  const RefinePlan p = refine_plan(n_points, stride, n_poses);
-  const uint32_t v[6] = {p.kept, p.tile, p.tiles, p.chunk, p.chunks, p.cap};
-  std::memcpy(out, v, sizeof(v));
-  return FMX_OK;
+  return plan_export(refine_plan(n_points, stride, n_poses), out);
 }
 
 // ---- surface normals of the dense map (normals_host.hpp)

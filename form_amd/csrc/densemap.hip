@@ -886,7 +886,7 @@ __device__ __forceinline__ void cube_visit(uint32_t lo, uint32_t hi, uint32_t gl
   }
 }
 
-// One point group's search, the per-trip body shared by k_nearest and k_align: the shell loop,
+// One point group's search, the per-trip body under search_winner: the shell loop,
 // the look-ahead loads, the group butterfly and the early stop, as described above.  cls: the
 // point's class (0: in range, p its world point and c its own voxel; anything else: no point
 // to search for, the group idles); gl: the lane's place in
@@ -941,6 +941,73 @@ __device__ __forceinline__ void nearest_search(int cls, double p0, double p1, do
   }
 }
 
+// A kept point of a search.  cls: -1 past the end, else probe_classify's class; p: the world
+// point, s: the sensor-frame point (both of a valid point), c: the own cell (of one in range).
+// Each kernel fills it in its own text: as a function of its own the same lines cost every one
+// of them its register allocation (DESIGN.md §Dense map, Refining, "One text").
+struct PointQuery {
+  int cls = -1;
+  double p0 = 0.0, p1 = 0.0, p2 = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  int c0 = 0, c1 = 0, c2 = 0;
+};
+// A search's winner: the bit pattern of its d2, its key and its slot; +inf, all ones (no stored
+// key is) and the dropped marker when nothing was admitted.
+constexpr unsigned long long kInfBits = 0x7FF0000000000000ull;
+struct Winner {
+  unsigned long long bits, key;
+  uint32_t slot;
+};
+// nearest_search for the point q; every lane of the group holds the group's winner.
+template <uint32_t L>
+__device__ __forceinline__ Winner search_winner(const PointQuery& q, uint32_t gl, const DenseArgs& a, const DenseTake& tk,
+                                                uint32_t reach, double max_d2, const uint32_t* __restrict__ offs,
+                                                const unsigned long long* __restrict__ keys,
+                                                const uint32_t* __restrict__ hits, const double* __restrict__ xyz,
+                                                unsigned long long& looked) {
+  Winner win{kInfBits, kDenseEmpty, kDenseDropped};
+  nearest_search<L>(q.cls, q.p0, q.p1, q.p2, q.c0, q.c1, q.c2, gl, a, tk, reach, max_d2, offs, keys, hits, xyz, win.bits,
+                    win.key, win.slot, looked);
+  return win;
+}
+__device__ __forceinline__ bool found(const PointQuery& q, const Winner& win) { return q.cls == 0 && win.key != kDenseEmpty; }
+// The state of a point that is there (q.cls >= 0): one of FMX_PROBE_*.
+__device__ __forceinline__ int point_state(const PointQuery& q, const Winner& win) {
+  return q.cls == 1 ? FMX_PROBE_INVALID : q.cls == 3 ? FMX_PROBE_OUT_OF_RANGE : found(q, win) ? FMX_PROBE_SOLID : FMX_PROBE_ABSENT;
+}
+
+constexpr int kAlignUnoriented = 5;  // a point's state beside FMX_PROBE_* (0 .. 4): found, winner without a normal
+
+// A wave's class counts, by ballots: the same in every lane of the wave (a wave meets fewer
+// than 2^32 points in all: n is below that).  st: the state in the lane that speaks for the
+// point, -1 in every other.
+struct ClassTally {
+  uint32_t found = 0, none = 0, oor = 0, inv = 0, unor = 0;
+  __device__ __forceinline__ void add(int st) {
+    unor += (uint32_t)__popcll(__ballot(st == kAlignUnoriented));
+    found += (uint32_t)__popcll(__ballot(st == FMX_PROBE_SOLID));
+    none += (uint32_t)__popcll(__ballot(st == FMX_PROBE_ABSENT));
+    oor += (uint32_t)__popcll(__ballot(st == FMX_PROBE_OUT_OF_RANGE));
+    inv += (uint32_t)__popcll(__ballot(st == FMX_PROBE_INVALID));
+  }
+  // cnt: {found, none, out_of_range, invalid, lookups, unoriented (kCounters = 6)}: one atomic
+  // per wave and counter, the lookups a wave sum (results unused: return-less).  Every lane calls.
+  template <int kCounters>
+  __device__ __forceinline__ void flush(unsigned long long* __restrict__ cnt, unsigned long long looked) const {
+    const unsigned long long w_looked = wave_sum(looked);
+    if ((threadIdx.x & 63) == 0) {
+      if (found) atomicAdd(&cnt[0], (unsigned long long)found);
+      if (none) atomicAdd(&cnt[1], (unsigned long long)none);
+      if (oor) atomicAdd(&cnt[2], (unsigned long long)oor);
+      if (inv) atomicAdd(&cnt[3], (unsigned long long)inv);
+      if (w_looked) atomicAdd(&cnt[4], w_looked);
+      if constexpr (kCounters == 6)
+        if (unor) atomicAdd(&cnt[5], (unsigned long long)unor);
+    }
+  }
+  // ... or the four into the wave's row of a block's LDS table (k_score), for one lane to call
+  __device__ __forceinline__ void store(uint32_t (&row)[4]) const { row[0] = found, row[1] = none, row[2] = oor, row[3] = inv; }
+};
+
 // cnt: {found, none, out_of_range, invalid, lookups}.  o.t takes dist2; o.step is not used.
 __global__ __launch_bounds__(kDenseThreads) void k_nearest(const float4* __restrict__ pts, uint32_t n, DenseArgs a,
                                                            DenseTake tk, uint32_t reach, double max_d2,
@@ -958,49 +1025,33 @@ __global__ __launch_bounds__(kDenseThreads) void k_nearest(const float4* __restr
   const unsigned long long g0 = ((unsigned long long)blockIdx.x * (unsigned long long)kDenseThreads + threadIdx.x) / L;
   const unsigned long long w0 = ((unsigned long long)blockIdx.x * (unsigned long long)kDenseThreads + (threadIdx.x & ~63u)) / L;
   const uint32_t gl = threadIdx.x & (L - 1u);  // the lane's place in its group
-  const unsigned long long inf_bits = 0x7FF0000000000000ull;
   unsigned long long looked = 0;
-  uint32_t n_found = 0, n_none = 0, n_oor = 0, n_inv = 0;  // (the same in every lane of the wave)
+  ClassTally tally;
   for (unsigned long long it = 0; w0 + it < (unsigned long long)n; it += stride) {
-    const unsigned long long q = g0 + it;
-    int cls = -1;  // past the end
-    double p0 = 0.0, p1 = 0.0, p2 = 0.0;
-    int c0 = 0, c1 = 0, c2 = 0;
-    if (q < (unsigned long long)n) {
+    const unsigned long long g = g0 + it;
+    PointQuery q;  // past the end
+    if (g < (unsigned long long)n) {
+      const float4 pf = pts[g];
       double wp[3];
       int v[3];
-      cls = probe_classify(pts[q], a, wp, v);
-      p0 = wp[0], p1 = wp[1], p2 = wp[2];
-      if (cls == 0) c0 = v[0], c1 = v[1], c2 = v[2];
+      q.cls = probe_classify(pf, a, wp, v);
+      q.p0 = wp[0], q.p1 = wp[1], q.p2 = wp[2];
+      if (q.cls == 0) q.c0 = v[0], q.c1 = v[1], q.c2 = v[2];
     }
-    unsigned long long b_bits = inf_bits, b_key = kDenseEmpty;  // (no stored key is all ones)
-    uint32_t b_slot = kDenseDropped;
-    nearest_search<L>(cls, p0, p1, p2, c0, c1, c2, gl, a, tk, reach, max_d2, offs, keys, hits, xyz, b_bits, b_key, b_slot,
-                      looked);
+    const Winner win = search_winner<L>(q, gl, a, tk, reach, max_d2, offs, keys, hits, xyz, looked);
     int st = -1;
-    if (cls >= 0 && gl == 0) {
-      const bool found = cls == 0 && b_key != kDenseEmpty;
-      st = cls == 1 ? FMX_PROBE_INVALID : cls == 3 ? FMX_PROBE_OUT_OF_RANGE : found ? FMX_PROBE_SOLID : FMX_PROBE_ABSENT;
-      const uint32_t i = (uint32_t)q;
+    if (q.cls >= 0 && gl == 0) {
+      const bool have = found(q, win);
+      st = point_state(q, win);
+      const uint32_t i = (uint32_t)g;
       o.state[i] = (uint8_t)st;
-      if (o.t) o.t[i] = __longlong_as_double((long long)(found ? b_bits : inf_bits));
-      const uint32_t slot = found ? b_slot : kDenseDropped;
-      probe_store(o, i, slot, (found && o.hits) ? hits[slot] : 0u, tk, tags, xyz);
+      if (o.t) o.t[i] = __longlong_as_double((long long)(have ? win.bits : kInfBits));
+      const uint32_t slot = have ? win.slot : kDenseDropped;
+      probe_store(o, i, slot, (have && o.hits) ? hits[slot] : 0u, tk, tags, xyz);
     }
-    // (a wave meets fewer than 2^32 points in all: n is below that)
-    n_found += (uint32_t)__popcll(__ballot(st == FMX_PROBE_SOLID));
-    n_none += (uint32_t)__popcll(__ballot(st == FMX_PROBE_ABSENT));
-    n_oor += (uint32_t)__popcll(__ballot(st == FMX_PROBE_OUT_OF_RANGE));
-    n_inv += (uint32_t)__popcll(__ballot(st == FMX_PROBE_INVALID));
+    tally.add(st);
   }
-  const unsigned long long w_looked = wave_sum(looked);
-  if ((threadIdx.x & 63) == 0) {  // results unused: return-less
-    if (n_found) atomicAdd(&cnt[0], (unsigned long long)n_found);
-    if (n_none) atomicAdd(&cnt[1], (unsigned long long)n_none);
-    if (n_oor) atomicAdd(&cnt[2], (unsigned long long)n_oor);
-    if (n_inv) atomicAdd(&cnt[3], (unsigned long long)n_inv);
-    if (w_looked) atomicAdd(&cnt[4], w_looked);
-  }
+  tally.flush<5>(cnt, looked);
 }
 
 // ---- aligning (DESIGN.md §Dense map, Aligning; include/fmx/fmx.h, fmx_align_system).  The
@@ -1010,15 +1061,16 @@ __global__ __launch_bounds__(kDenseThreads) void k_nearest(const float4* __restr
 //
 // A group of FMX_ALIGN_LANES adjacent lanes serves one kept point; group g has point
 // i = g * every (the points in between are skipped: never loaded), so a strided launch is dense
-// in lanes.  The search is nearest_search, the winner stays in registers; the group's first
-// lane loads the winner's representative q and adds the three rows of point_row<1> (X(i) the
-// identity, p_i = q, p_j the sensor-frame point) into 28 fp64 accumulators that persist over
-// the grid-stride trips.  The reduction is k_linearize_total's (linearize.hip): the wave's
-// reduce-scatter, the block's waves added in wave order through LDS, the block partial out with
+// in lanes.  The point is a PointQuery, the search search_winner's, the winner stays in
+// registers; the group's first lane runs the row step (add_rows: the winner's representative q
+// loaded, the three rows of point_row<1> with X(i) the identity, p_i = q, p_j the sensor-frame
+// point) into 28 fp64 accumulators that persist over the grid-stride trips.  The reduction is
+// k_linearize_total's (linearize.hip): the block's sums (block_sums28: the wave's reduce-scatter,
+// the block's waves added in wave order through LDS), the block partial out with
 // agent-scope stores, an agent-scope ticket, the last block summing the partials in block
 // order and writing the system, and the counters, to mapped host memory behind the completion
 // word.  Every sum's order is fixed by n, every and the grid: the bits do not depend on the
-// order the lanes run in.  The class counts are one return-less atomic per wave and counter.
+// order the lanes run in.  The class counts are ClassTally's, as k_nearest's.
 #ifndef FMX_ALIGN_LANES
 #define FMX_ALIGN_LANES 1
 #endif
@@ -1033,7 +1085,8 @@ namespace {
 }  // namespace
 
 //
-// The row kind is the kernel's template parameter.  PointRows: the three point-to-point rows
+// The row kind is the template parameter of k_align, of k_refine and of the row step they
+// share.  PointRows: the three point-to-point rows
 // above.  PlaneRows (DESIGN.md §Dense map, Plane alignment; fmx_plane_system): the winner's
 // slot also names its record of the normal snapshot (16 B more per found point); a winner
 // without a normal makes the point *unoriented* (a sixth counter, nothing added), any other
@@ -1045,7 +1098,53 @@ struct PlaneRows {
   static constexpr int kCounters = 6;
   const float4* __restrict__ nrm;  // per slot: {n0, n1, n2, flatness}, all-zero n unless oriented
 };
-constexpr int kAlignUnoriented = 5;  // a point's class beside FMX_PROBE_* (0 .. 4): found, winner without a normal
+
+// The row step, for the lane that speaks for a found point: the winner's representative q
+// loaded, the rows of the kind added into acc (inv: 1 / sigma).  Returns the point's state:
+// FMX_PROBE_SOLID, or kAlignUnoriented (PlaneRows: the winner has no normal, nothing added).
+template <class Rows>
+__device__ __forceinline__ int add_rows(const Rows& rows, const DenseArgs& a, const PointQuery& p, const Winner& win,
+                                        const double* __restrict__ xyz, double inv, double (&acc)[32]) {
+  const double q[3] = {xyz[3 * (size_t)win.slot + 0], xyz[3 * (size_t)win.slot + 1], xyz[3 * (size_t)win.slot + 2]};
+  const double pj[3] = {p.s0, p.s1, p.s2}, wpj[3] = {p.p0, p.p1, p.p2};
+  double H[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) H[i] = 0.0;
+  if constexpr (Rows::kCounters == 6) {
+    const float4 nf = rows.nrm[win.slot];
+    if (nf.x == 0.0f && nf.y == 0.0f && nf.z == 0.0f) return kAlignUnoriented;
+    const double ni[3] = {(double)nf.x, (double)nf.y, (double)nf.z};
+    const double eye[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};  // X(i)
+    double r;
+    plane_row<1>(eye, a.T.m, q, ni, pj, r, H);
+    accum_row<1>(H, r, inv, acc);
+  } else {
+#pragma unroll
+    for (int r3 = 0; r3 < 3; ++r3) {
+      double r;
+      point_row<1>(a.T.m, a.T.m, q, pj, q, wpj, r3, r, H);  // (X(i) is not read in this mode)
+      accum_row<1>(H, r, inv, acc);
+    }
+  }
+  return FMX_PROBE_SOLID;
+}
+
+// The block's 28 sums of its lanes' acc: the wave's reduce-scatter (entry lane / 2 in the even
+// lanes), then the waves added in wave order through sw.  Entry t is returned in thread t < 28
+// (0.0 in the others); one barrier, which also covers what the caller stored to LDS before.
+__device__ __forceinline__ double block_sums28(double (&acc)[32], double (*sw)[28]) {
+  const int w = threadIdx.x / kWave, lane = lane_id();
+  const double mine = wave_reduce_scatter32(acc);
+  if ((lane & 1) == 0 && (lane >> 1) < 28) sw[w][lane >> 1] = mine;
+  __syncthreads();
+  double bp = 0.0;
+  if (threadIdx.x < 28) {
+    bp = sw[0][threadIdx.x];
+#pragma unroll
+    for (int i = 1; i < kDenseThreads / kWave; ++i) bp += sw[i][threadIdx.x];
+  }
+  return bp;
+}
 
 // m: the kept points, ceil(n / every).  cnt: {found, none, out_of_range, invalid, lookups,
 // unoriented (PlaneRows)}, zeroed by the caller.  ticket: 0 at launch, 0 again afterwards.  out:
@@ -1060,7 +1159,6 @@ __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restric
                                                          unsigned long long* __restrict__ cnt, double* __restrict__ bpart,
                                                          uint32_t* __restrict__ ticket, double* __restrict__ out,
                                                          uint32_t* __restrict__ flag, uint32_t seq, Rows rows) {
-  constexpr bool kPlane = Rows::kCounters == 6;
   constexpr uint32_t L = (uint32_t)FMX_ALIGN_LANES;
   constexpr int NG = 28;
   constexpr int kGroups = kDenseThreads / NG;  // final reduction: lane groups x 28 entries
@@ -1068,93 +1166,39 @@ __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restric
   const unsigned long long g0 = ((unsigned long long)blockIdx.x * (unsigned long long)kDenseThreads + threadIdx.x) / L;
   const unsigned long long w0 = ((unsigned long long)blockIdx.x * (unsigned long long)kDenseThreads + (threadIdx.x & ~63u)) / L;
   const uint32_t gl = threadIdx.x & (L - 1u);
-  const unsigned long long inf_bits = 0x7FF0000000000000ull;
   unsigned long long looked = 0;
-  uint32_t n_found = 0, n_none = 0, n_oor = 0, n_inv = 0;  // (the same in every lane of the wave)
-  [[maybe_unused]] uint32_t n_unor = 0;
+  ClassTally tally;
   double acc[32];
 #pragma unroll
   for (int i = 0; i < 32; ++i) acc[i] = 0.0;
   for (unsigned long long it = 0; w0 + it < (unsigned long long)m; it += stride) {
     const unsigned long long g = g0 + it;
-    int cls = -1;  // past the end
-    double p0 = 0.0, p1 = 0.0, p2 = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    int c0 = 0, c1 = 0, c2 = 0;
+    PointQuery q;  // past the end
     if (g < (unsigned long long)m) {
       const float4 pf = pts[g * (unsigned long long)every];  // (g < m: the index is below n)
       double wp[3];
       int v[3];
-      cls = probe_classify(pf, a, wp, v);
-      p0 = wp[0], p1 = wp[1], p2 = wp[2];
-      s0 = (double)pf.x, s1 = (double)pf.y, s2 = (double)pf.z;
-      if (cls == 0) c0 = v[0], c1 = v[1], c2 = v[2];
+      q.cls = probe_classify(pf, a, wp, v);
+      q.p0 = wp[0], q.p1 = wp[1], q.p2 = wp[2];
+      q.s0 = (double)pf.x, q.s1 = (double)pf.y, q.s2 = (double)pf.z;
+      if (q.cls == 0) q.c0 = v[0], q.c1 = v[1], q.c2 = v[2];
     }
-    unsigned long long b_bits = inf_bits, b_key = kDenseEmpty;
-    uint32_t b_slot = kDenseDropped;
-    nearest_search<L>(cls, p0, p1, p2, c0, c1, c2, gl, a, tk, reach, max_d2, offs, keys, hits, xyz, b_bits, b_key, b_slot,
-                      looked);
+    const Winner win = search_winner<L>(q, gl, a, tk, reach, max_d2, offs, keys, hits, xyz, looked);
     int st = -1;
-    if (cls >= 0 && gl == 0) {
-      const bool found = cls == 0 && b_key != kDenseEmpty;
-      st = cls == 1 ? FMX_PROBE_INVALID : cls == 3 ? FMX_PROBE_OUT_OF_RANGE : found ? FMX_PROBE_SOLID : FMX_PROBE_ABSENT;
-      if (found) {
-        const double q[3] = {xyz[3 * (size_t)b_slot + 0], xyz[3 * (size_t)b_slot + 1], xyz[3 * (size_t)b_slot + 2]};
-        const double pj[3] = {s0, s1, s2}, wpj[3] = {p0, p1, p2};
-        double H[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) H[i] = 0.0;
-        if constexpr (kPlane) {
-          const float4 nf = rows.nrm[b_slot];
-          if (nf.x == 0.0f && nf.y == 0.0f && nf.z == 0.0f) {
-            st = kAlignUnoriented;
-          } else {
-            const double ni[3] = {(double)nf.x, (double)nf.y, (double)nf.z};
-            const double eye[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};  // X(i)
-            double r;
-            plane_row<1>(eye, a.T.m, q, ni, pj, r, H);
-            accum_row<1>(H, r, inv, acc);
-          }
-        } else {
-#pragma unroll
-          for (int r3 = 0; r3 < 3; ++r3) {
-            double r;
-            point_row<1>(a.T.m, a.T.m, q, pj, q, wpj, r3, r, H);  // (X(i) is not read in this mode)
-            accum_row<1>(H, r, inv, acc);
-          }
-        }
-      }
+    if (q.cls >= 0 && gl == 0) {
+      st = point_state(q, win);
+      if (st == FMX_PROBE_SOLID) st = add_rows(rows, a, q, win, xyz, inv, acc);
     }
-    if constexpr (kPlane) n_unor += (uint32_t)__popcll(__ballot(st == kAlignUnoriented));
-    n_found += (uint32_t)__popcll(__ballot(st == FMX_PROBE_SOLID));
-    n_none += (uint32_t)__popcll(__ballot(st == FMX_PROBE_ABSENT));
-    n_oor += (uint32_t)__popcll(__ballot(st == FMX_PROBE_OUT_OF_RANGE));
-    n_inv += (uint32_t)__popcll(__ballot(st == FMX_PROBE_INVALID));
+    tally.add(st);
   }
-  const unsigned long long w_looked = wave_sum(looked);
-  if ((threadIdx.x & 63) == 0) {  // results unused: return-less
-    if (n_found) atomicAdd(&cnt[0], (unsigned long long)n_found);
-    if (n_none) atomicAdd(&cnt[1], (unsigned long long)n_none);
-    if (n_oor) atomicAdd(&cnt[2], (unsigned long long)n_oor);
-    if (n_inv) atomicAdd(&cnt[3], (unsigned long long)n_inv);
-    if (w_looked) atomicAdd(&cnt[4], w_looked);
-    if constexpr (kPlane)
-      if (n_unor) atomicAdd(&cnt[5], (unsigned long long)n_unor);
-  }
+  tally.flush<Rows::kCounters>(cnt, looked);
   __shared__ double sw[kAlignWaves][NG];
   __shared__ double sq[kGroups][NG];
   __shared__ int s_last;
-  const int w = threadIdx.x / kWave, lane = lane_id();
-  const double mine = wave_reduce_scatter32(acc);  // entry lane / 2
-  if ((lane & 1) == 0 && (lane >> 1) < NG) sw[w][lane >> 1] = mine;
-  __syncthreads();
-  if (threadIdx.x < NG) {
-    const int t = threadIdx.x;
-    double bp = sw[0][t];
-#pragma unroll
-    for (int i = 1; i < kAlignWaves; ++i) bp += sw[i][t];
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(bpart + (size_t)blockIdx.x * kAlignLd + t),
+  const double bp = block_sums28(acc, sw);
+  if (threadIdx.x < NG)
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(bpart + (size_t)blockIdx.x * kAlignLd + threadIdx.x),
                        (unsigned long long)__double_as_longlong(bp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
   // every wave's partial stores and counter atomics are acknowledged before its block's ticket
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -1204,10 +1248,10 @@ __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restric
 // neighbouring poses of the list; FMX_SCORE_TILE_MAJOR=0 builds the pose-major order, 8 to 15 %
 // slower at 1024 poses in tools/score_cost.py --ab: the records are the same bits either way)
 // and a block walks them with a grid stride under k_nearest's cap.  The item's pose comes
-// from the staged pose array and is uniform over the block; the DenseArgs around it goes to
-// probe_classify and nearest_search unchanged.  Reduction, every order fixed: a wave's d2 by
+// from the staged pose array and is uniform over the block (item_pose); the DenseArgs around it
+// goes to probe_classify and search_winner unchanged.  Reduction, every order fixed: a wave's d2 by
 // wave_sum's xor butterfly (a point that found nothing adds +0.0: exact), its counts by
-// ballots, then the block's waves in wave order through LDS, one partial record per item.
+// ClassTally's ballots over point_state (the predicate k_nearest and k_align count by), then the block's waves in wave order through LDS, one partial record per item.
 // k_score_finish then sums a pose's tiles: one wave per pose, lane l takes tiles l, l + 64, ...
 // in that order, then the same butterfly.  Which block ran an item, how many poses the chunk
 // holds and where the pose stands in it enter neither: a record depends on the points, the
@@ -1217,8 +1261,23 @@ __global__ __launch_bounds__(kDenseThreads) void k_align(const float4* __restric
 #define FMX_SCORE_TILE_MAJOR 1
 #endif
 static_assert(kScoreTile == (uint32_t)kDenseThreads, "a tile is one block-wide pass");
-static_assert(kScoreGridCap == (uint32_t)kNearestBlocks, "the score grid is capped as k_nearest's");
+static_assert(kBatchGridCap == (uint32_t)kNearestBlocks, "the score and refine grids are capped as k_nearest's");
 constexpr int kScoreWaves = kDenseThreads / kWave;
+
+// Work item `item` of `items` = poses of the chunk * tiles (uniform over the block): its tile
+// and pose in the order above, the pose's 12 doubles from the staged array into a.T.  Shared by
+// k_score and k_refine (FMX_SCORE_TILE_MAJOR=0 reorders both; their records do not change).
+__device__ __forceinline__ void item_pose(uint32_t item, uint32_t items, uint32_t tiles, const double* __restrict__ poses,
+                                          DenseArgs& a, uint32_t& tile, uint32_t& pose) {
+#if FMX_SCORE_TILE_MAJOR
+  const uint32_t n_poses = items / tiles;
+  tile = item / n_poses, pose = item - tile * n_poses;
+#else
+  pose = item / tiles, tile = item - pose * tiles;
+#endif
+#pragma unroll
+  for (int k = 0; k < 12; ++k) a.T.m[k] = poses[(size_t)pose * 12 + k];
+}
 
 // m: the kept points; tiles = ceil(m / kScoreTile); items = poses of the chunk * tiles.
 // part[pose * tiles + tile]: written whole by the item's block.
@@ -1233,40 +1292,30 @@ __global__ __launch_bounds__(kDenseThreads) void k_score(const float4* __restric
   __shared__ double s_d2[kScoreWaves];
   __shared__ unsigned long long s_look[kScoreWaves];
   __shared__ uint32_t s_cnt[kScoreWaves][4];
-  const unsigned long long inf_bits = 0x7FF0000000000000ull;
   const int w = threadIdx.x / kWave;
   for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {  // (uniform over the block)
-#if FMX_SCORE_TILE_MAJOR
-    const uint32_t n_poses = items / tiles, tile = item / n_poses, pose = item - tile * n_poses;
-#else
-    const uint32_t pose = item / tiles, tile = item - pose * tiles;
-#endif
-#pragma unroll
-    for (int k = 0; k < 12; ++k) a.T.m[k] = poses[(size_t)pose * 12 + k];
+    uint32_t tile, pose;
+    item_pose(item, items, tiles, poses, a, tile, pose);
     const unsigned long long g = (unsigned long long)tile * kScoreTile + threadIdx.x;
-    int cls = -1;  // past the end
-    double p0 = 0.0, p1 = 0.0, p2 = 0.0;
-    int c0 = 0, c1 = 0, c2 = 0;
+    PointQuery q;  // past the end
     if (g < (unsigned long long)m) {
+      const float4 pf = pts[g * (unsigned long long)every];  // (g < m: the index is below n)
       double wp[3];
       int v[3];
-      cls = probe_classify(pts[g * (unsigned long long)every], a, wp, v);  // (g < m: the index is below n)
-      p0 = wp[0], p1 = wp[1], p2 = wp[2];
-      if (cls == 0) c0 = v[0], c1 = v[1], c2 = v[2];
+      q.cls = probe_classify(pf, a, wp, v);
+      q.p0 = wp[0], q.p1 = wp[1], q.p2 = wp[2];
+      if (q.cls == 0) q.c0 = v[0], q.c1 = v[1], q.c2 = v[2];
     }
-    unsigned long long b_bits = inf_bits, b_key = kDenseEmpty, looked = 0;
-    uint32_t b_slot = kDenseDropped;
-    nearest_search<1u>(cls, p0, p1, p2, c0, c1, c2, 0u, a, tk, reach, max_d2, offs, keys, hits, xyz, b_bits, b_key, b_slot,
-                       looked);
-    const bool found = cls == 0 && b_key != kDenseEmpty;
-    const double wd = wave_sum(found ? __longlong_as_double((long long)b_bits) : 0.0);
+    unsigned long long looked = 0;
+    const Winner win = search_winner<1u>(q, 0u, a, tk, reach, max_d2, offs, keys, hits, xyz, looked);
+    const double wd = wave_sum(found(q, win) ? __longlong_as_double((long long)win.bits) : 0.0);
     const unsigned long long wl = wave_sum(looked);
-    const uint32_t n_found = (uint32_t)__popcll(__ballot(found)), n_none = (uint32_t)__popcll(__ballot(cls == 0 && !found)),
-                   n_oor = (uint32_t)__popcll(__ballot(cls == 3)), n_inv = (uint32_t)__popcll(__ballot(cls == 1));
+    ClassTally tally;
+    tally.add(q.cls >= 0 ? point_state(q, win) : -1);
     if ((threadIdx.x & 63) == 0) {
       s_d2[w] = wd;
       s_look[w] = wl;
-      s_cnt[w][0] = n_found, s_cnt[w][1] = n_none, s_cnt[w][2] = n_oor, s_cnt[w][3] = n_inv;
+      tally.store(s_cnt[w]);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1312,21 +1361,19 @@ __global__ __launch_bounds__(kDenseThreads) void k_score_finish(const fmx_pose_s
 // k_score's item scheme with k_align's rows.  A work item is one pose and one tile of
 // kRefineTile kept points (refine_host.hpp), the items of a chunk tile-major, a block walking
 // them with a grid stride under k_nearest's cap; the item's pose comes from the staged pose
-// array, uniform over the block, into the DenseArgs that probe_classify and nearest_search<1>
-// take unchanged.  A tile is kRefineTile / 256 block-wide passes: one lane per kept point and
-// pass, the rows built exactly as k_align builds them (the same factor_rows.hpp calls with the
-// same arguments, the unoriented test on the winner's normal record included) into 28 fp64
+// array, uniform over the block, into the DenseArgs (item_pose) that probe_classify and
+// search_winner<1> take unchanged.  A tile is kRefineTile / 256 block-wide passes: one lane per
+// kept point and pass, the rows added by add_rows, the row step k_align calls, into 28 fp64
 // accumulators that are reset per item and persist over its passes, as k_align's over its
-// trips.  Per item one reduction: the wave's reduce-scatter, then the block's waves in wave
-// order through LDS; the counts by ballots.  One partial record per item, written whole by the
+// trips.  Per item one reduction: block_sums28, as k_align's per block; the counts by
+// ballots over point_state's states (in this kernel's own text: see below).  One partial record per item, written whole by the
 // item's block (an item that found nothing writes zeros: the finisher reads every record).
-// k_refine_finish sums a pose's tiles in an order fixed by their number, one block per pose.  Every order is fixed
-// by the kept points and the tile: which block ran an item, how many poses the chunk holds and
+// k_refine_finish sums a pose's tiles in an order fixed by their number, one block per pose.
+// Every order is fixed by the kept points and the tile: which block ran an item, how many poses the chunk holds and
 // where the pose stands in it enter nothing.  The launch boundary is the hand-off: no ticket, no
 // agent-scope protocol, no floating-point atomic; nothing is shared with k_align's partials,
 // ticket and counters or with the score buffers.
 static_assert(kRefineTile % (uint32_t)kDenseThreads == 0, "a tile is a whole number of block-wide passes");
-static_assert(kRefineGridCap == (uint32_t)kNearestBlocks, "the refine grid is capped as k_nearest's");
 constexpr int kRefineWaves = kDenseThreads / kWave;
 constexpr uint32_t kRefinePasses = kRefineTile / (uint32_t)kDenseThreads;
 
@@ -1341,20 +1388,19 @@ __global__ __launch_bounds__(kDenseThreads) void k_refine(const float4* __restri
                                                           const uint32_t* __restrict__ hits,
                                                           const double* __restrict__ xyz, RefinePart* __restrict__ part,
                                                           Rows rows) {
-  constexpr bool kPlane = Rows::kCounters == 6;
   constexpr int NG = 28;
   __shared__ double sw[kRefineWaves][NG];
   __shared__ unsigned long long s_look[kRefineWaves];
   __shared__ uint32_t s_cnt[kRefineWaves][5];
-  const unsigned long long inf_bits = 0x7FF0000000000000ull;
-  const int w = threadIdx.x / kWave, lane = lane_id();
-  const uint32_t n_poses = items / tiles;
+  const int w = threadIdx.x / kWave;
   for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {  // (uniform over the block)
-    const uint32_t tile = item / n_poses, pose = item - tile * n_poses;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) a.T.m[k] = poses[(size_t)pose * 12 + k];
+    uint32_t tile, pose;
+    item_pose(item, items, tiles, poses, a, tile, pose);
     unsigned long long looked = 0;
-    uint32_t n_found = 0, n_none = 0, n_oor = 0, n_inv = 0, n_unor = 0;  // (the same in every lane of the wave)
+    // (the same in every lane of the wave.  ClassTally's counts, in this kernel's own text: with
+    // the struct the kernel allocates 103 / 133 VGPRs, not 144 / 213, and runs at another
+    // occupancy, faster for some batch sizes and slower for others)
+    uint32_t n_found = 0, n_none = 0, n_oor = 0, n_inv = 0, n_unor = 0;
     double acc[32];
 #pragma unroll
     for (int i = 0; i < 32; ++i) acc[i] = 0.0;
@@ -1363,74 +1409,37 @@ __global__ __launch_bounds__(kDenseThreads) void k_refine(const float4* __restri
       const unsigned long long off = (unsigned long long)ps * kDenseThreads;
       if (w0 + off >= (unsigned long long)m) break;  // (uniform over the wave)
       const unsigned long long g = w0 + off + (threadIdx.x & 63u);
-      int cls = -1;  // past the end
-      double p0 = 0.0, p1 = 0.0, p2 = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
-      int c0 = 0, c1 = 0, c2 = 0;
+      PointQuery q;  // past the end
       if (g < (unsigned long long)m) {
         const float4 pf = pts[g * (unsigned long long)every];  // (g < m: the index is below n)
         double wp[3];
         int v[3];
-        cls = probe_classify(pf, a, wp, v);
-        p0 = wp[0], p1 = wp[1], p2 = wp[2];
-        s0 = (double)pf.x, s1 = (double)pf.y, s2 = (double)pf.z;
-        if (cls == 0) c0 = v[0], c1 = v[1], c2 = v[2];
+        q.cls = probe_classify(pf, a, wp, v);
+        q.p0 = wp[0], q.p1 = wp[1], q.p2 = wp[2];
+        q.s0 = (double)pf.x, q.s1 = (double)pf.y, q.s2 = (double)pf.z;
+        if (q.cls == 0) q.c0 = v[0], q.c1 = v[1], q.c2 = v[2];
       }
-      unsigned long long b_bits = inf_bits, b_key = kDenseEmpty;
-      uint32_t b_slot = kDenseDropped;
-      nearest_search<1u>(cls, p0, p1, p2, c0, c1, c2, 0u, a, tk, reach, max_d2, offs, keys, hits, xyz, b_bits, b_key, b_slot,
-                         looked);
+      const Winner win = search_winner<1u>(q, 0u, a, tk, reach, max_d2, offs, keys, hits, xyz, looked);
       int st = -1;
-      if (cls >= 0) {
-        const bool found = cls == 0 && b_key != kDenseEmpty;
-        st = cls == 1 ? FMX_PROBE_INVALID : cls == 3 ? FMX_PROBE_OUT_OF_RANGE : found ? FMX_PROBE_SOLID : FMX_PROBE_ABSENT;
-        if (found) {
-          const double q[3] = {xyz[3 * (size_t)b_slot + 0], xyz[3 * (size_t)b_slot + 1], xyz[3 * (size_t)b_slot + 2]};
-          const double pj[3] = {s0, s1, s2}, wpj[3] = {p0, p1, p2};
-          double H[12];
-#pragma unroll
-          for (int i = 0; i < 12; ++i) H[i] = 0.0;
-          if constexpr (kPlane) {
-            const float4 nf = rows.nrm[b_slot];
-            if (nf.x == 0.0f && nf.y == 0.0f && nf.z == 0.0f) {
-              st = kAlignUnoriented;
-            } else {
-              const double ni[3] = {(double)nf.x, (double)nf.y, (double)nf.z};
-              const double eye[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};  // X(i)
-              double r;
-              plane_row<1>(eye, a.T.m, q, ni, pj, r, H);
-              accum_row<1>(H, r, inv, acc);
-            }
-          } else {
-#pragma unroll
-            for (int r3 = 0; r3 < 3; ++r3) {
-              double r;
-              point_row<1>(a.T.m, a.T.m, q, pj, q, wpj, r3, r, H);  // (X(i) is not read in this mode)
-              accum_row<1>(H, r, inv, acc);
-            }
-          }
-        }
+      if (q.cls >= 0) {
+        st = point_state(q, win);
+        if (st == FMX_PROBE_SOLID) st = add_rows(rows, a, q, win, xyz, inv, acc);
       }
-      if constexpr (kPlane) n_unor += (uint32_t)__popcll(__ballot(st == kAlignUnoriented));
+      if constexpr (Rows::kCounters == 6) n_unor += (uint32_t)__popcll(__ballot(st == kAlignUnoriented));
       n_found += (uint32_t)__popcll(__ballot(st == FMX_PROBE_SOLID));
       n_none += (uint32_t)__popcll(__ballot(st == FMX_PROBE_ABSENT));
       n_oor += (uint32_t)__popcll(__ballot(st == FMX_PROBE_OUT_OF_RANGE));
       n_inv += (uint32_t)__popcll(__ballot(st == FMX_PROBE_INVALID));
     }
     const unsigned long long wl = wave_sum(looked);
-    const double mine = wave_reduce_scatter32(acc);  // entry lane / 2
-    if ((lane & 1) == 0 && (lane >> 1) < NG) sw[w][lane >> 1] = mine;
-    if (lane == 0) {
+    if (lane_id() == 0) {
       s_look[w] = wl;
       s_cnt[w][0] = n_found, s_cnt[w][1] = n_none, s_cnt[w][2] = n_oor, s_cnt[w][3] = n_inv, s_cnt[w][4] = n_unor;
     }
-    __syncthreads();
+    const double bp = block_sums28(acc, sw);
     RefinePart* const rec = part + ((size_t)pose * tiles + tile);
     if (threadIdx.x < NG) {
-      const int t = threadIdx.x;
-      double bp = sw[0][t];
-#pragma unroll
-      for (int i = 1; i < kRefineWaves; ++i) bp += sw[i][t];  // in wave order
-      rec->S[t] = bp;
+      rec->S[threadIdx.x] = bp;
     } else if (threadIdx.x >= 32 && threadIdx.x < 32 + 5) {
       const int k = threadIdx.x - 32;
       uint32_t s = s_cnt[0][k];
@@ -1785,6 +1794,26 @@ static DenseArgs dense_args(const fmx_ctx* c, const double* pose34) {
   return a;
 }
 
+// The grid of a scan over the table's slots: one lane per slot up to kDenseScanBlocks blocks, a
+// grid stride beyond.
+static uint32_t scan_blocks(uint64_t slots) {
+  return (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (slots + kDenseThreads - 1) / kDenseThreads);
+}
+// The grid of a search that wants `want` blocks: capped (kNearestBlocks), a grid stride beyond.
+static uint32_t capped_blocks(unsigned long long want) {
+  return (uint32_t)std::min<unsigned long long>(want, (unsigned long long)kNearestBlocks);
+}
+// The cube's offsets in shell order on the device, once per context, whichever search or
+// normals build comes first (the host copy outlives the transfer).
+static const uint32_t* offsets_on_device(fmx_ctx* c, hipStream_t st) {
+  auto& N = c->dense.nearest;
+  if (!N.have) {
+    FMX_HIP(hipMemcpyAsync(N.offs.p, N.h_offs.data(), N.h_offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    N.have = true;
+  }
+  return N.offs.p;
+}
+
 // Claim + fill of the n points at d_pts (n > 0, capacity checked by the caller) at pose34 as
 // integration number seq, on stream st.  The counts, the voxel total and the completion word
 // (flag_seq at c->dense.h_res[7]) land in c->dense.h_res once the fill's last block is through.
@@ -1888,16 +1917,12 @@ void run_probe_rays(fmx_ctx* c, const float4* d_pts, size_t n, const double* pos
 void run_nearest(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34, const ProbeFilter& f, uint32_t reach,
                  double max_dist2, const ProbeOut& o, hipStream_t st) {
   auto& D = c->dense;
-  auto& N = D.nearest;
-  if (!N.have) {  // the cube's offsets in shell order, once per context (the host copy outlives the transfer)
-    FMX_HIP(hipMemcpyAsync(N.offs.p, N.h_offs.data(), N.h_offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    N.have = true;
-  }
+  const uint32_t* offs = offsets_on_device(c, st);
   const DenseArgs a = dense_args(c, pose34);
   // one group of lanes per point up to kNearestBlocks blocks (8 waves on every SIMD of 256 CUs), a grid
   // stride beyond: the counters' same-address atomics, one per wave, bound the launch otherwise
   const unsigned long long want = ((unsigned long long)n * FMX_NEAREST_LANES + kDenseThreads - 1) / kDenseThreads;
-  const uint32_t blocks = (uint32_t)(want < (unsigned long long)kNearestBlocks ? want : (unsigned long long)kNearestBlocks);
+  const uint32_t blocks = capped_blocks(want);
   FMX_HIP(hipMemsetAsync(D.probe.cnt.p, 0, 8 * sizeof(unsigned long long), st));
   // DESIGN.md §Dense map, Nearest: the point (16), the own cell's key word (8) and what is
   // written per point; the other cells' 8 B per lookup, + 4 (+ 4 under a ratio) per present
@@ -1905,7 +1930,7 @@ void run_nearest(fmx_ctx* c, const float4* d_pts, size_t n, const double* pose34
   // `lookups` gives the first)
   ProfScope ps(c->prof, PROF_DENSE, (double)n * (24.0 + probe_out_bytes(o)), st);
   hipLaunchKernelGGL(k_nearest, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)n, a, probe_take_args(c, f),
-                     reach, max_dist2, N.offs.p, D.keys.p, D.tags.p, D.hits.p, D.xyz.p, o, D.probe.cnt.p);
+                     reach, max_dist2, offs, D.keys.p, D.tags.p, D.hits.p, D.xyz.p, o, D.probe.cnt.p);
   FMX_HIP(hipGetLastError());
 }
 
@@ -1916,17 +1941,13 @@ static void launch_align(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t eve
                          const ProbeFilter& f, uint32_t reach, double max_dist2, double sigma, uint32_t seq, hipStream_t st,
                          Rows rows) {
   auto& D = c->dense;
-  auto& N = D.nearest;
   auto& A = D.align;
-  if (!N.have) {  // the cube's offsets in shell order, once per context (shared with run_nearest)
-    FMX_HIP(hipMemcpyAsync(N.offs.p, N.h_offs.data(), N.h_offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    N.have = true;
-  }
+  const uint32_t* offs = offsets_on_device(c, st);
   const DenseArgs a = dense_args(c, pose34);
   const unsigned long long m = ((unsigned long long)n + every - 1) / every;  // the kept points
   // the grid of run_nearest over the kept points: capped, a grid stride beyond
   const unsigned long long want = (m * FMX_ALIGN_LANES + kDenseThreads - 1) / kDenseThreads;
-  const uint32_t blocks = (uint32_t)(want < (unsigned long long)kNearestBlocks ? want : (unsigned long long)kNearestBlocks);
+  const uint32_t blocks = capped_blocks(want);
   FMX_HIP(hipMemsetAsync(A.cnt.p, 0, 8 * sizeof(unsigned long long), st));
   // DESIGN.md §Dense map, Aligning: run_nearest's model without the per-point outputs (the
   // point, 16, and the own cell's key word, 8; the other lookups are not known at launch), plus
@@ -1934,7 +1955,7 @@ static void launch_align(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t eve
   // found point are not known at launch
   ProfScope ps(c->prof, PROF_DENSE, (double)m * 24.0 + (double)blocks * 2.0 * 28.0 * sizeof(double), st);
   hipLaunchKernelGGL(k_align<Rows>, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, (uint32_t)m, every, a,
-                     probe_take_args(c, f), reach, max_dist2, 1.0 / sigma, N.offs.p, D.keys.p, D.hits.p, D.xyz.p, A.cnt.p,
+                     probe_take_args(c, f), reach, max_dist2, 1.0 / sigma, offs, D.keys.p, D.hits.p, D.xyz.p, A.cnt.p,
                      A.bpart.p, A.ticket.p, A.h_out.d, c->h_flag.d, seq, rows);
   FMX_HIP(hipGetLastError());
 }
@@ -1952,24 +1973,19 @@ void run_plane(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, const 
 void run_score(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, uint32_t poses, const ProbeFilter& f,
                uint32_t reach, double max_dist2, hipStream_t st) {
   auto& D = c->dense;
-  auto& N = D.nearest;
   auto& S = D.score;
-  if (!N.have) {  // the cube's offsets in shell order, once per context (shared with run_nearest)
-    FMX_HIP(hipMemcpyAsync(N.offs.p, N.h_offs.data(), N.h_offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    N.have = true;
-  }
-  const double eye[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
-  const DenseArgs a = dense_args(c, eye);  // (the kernel puts each item's pose in)
+  const uint32_t* offs = offsets_on_device(c, st);
+  const DenseArgs a = dense_args(c, kEye34);  // (the kernel puts each item's pose in)
   const ScorePlan plan = score_plan((unsigned long long)n, every, poses);
   const unsigned long long items = (unsigned long long)poses * plan.tiles;  // (at most 2^24: score_plan's chunk)
   {
-    const uint32_t blocks = (uint32_t)(items < (unsigned long long)kNearestBlocks ? items : (unsigned long long)kNearestBlocks);
+    const uint32_t blocks = capped_blocks(items);
     // DESIGN.md §Dense map, Scoring: run_align's model per (pose, kept point) (the point, 16, and
     // the own cell's key word, 8; the other lookups are not known at launch), the item's pose
     // (96) and its partial record (32)
     ProfScope ps(c->prof, PROF_DENSE, (double)poses * (double)plan.kept * 24.0 + (double)items * 128.0, st);
     hipLaunchKernelGGL(k_score, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, plan.kept, every, S.poses.p, plan.tiles,
-                       (uint32_t)items, a, probe_take_args(c, f), reach, max_dist2, N.offs.p, D.keys.p, D.hits.p, D.xyz.p,
+                       (uint32_t)items, a, probe_take_args(c, f), reach, max_dist2, offs, D.keys.p, D.hits.p, D.xyz.p,
                        S.part.p);
     FMX_HIP(hipGetLastError());
   }
@@ -1985,18 +2001,13 @@ void run_score(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, uint32
 void run_refine(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, uint32_t poses, const ProbeFilter& f,
                 uint32_t reach, double max_dist2, double sigma, bool plane, hipStream_t st) {
   auto& D = c->dense;
-  auto& N = D.nearest;
   auto& Rf = D.refine;
-  if (!N.have) {  // the cube's offsets in shell order, once per context (shared with run_nearest)
-    FMX_HIP(hipMemcpyAsync(N.offs.p, N.h_offs.data(), N.h_offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    N.have = true;
-  }
-  const double eye[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
-  const DenseArgs a = dense_args(c, eye);  // (the kernel puts each item's pose in)
+  const uint32_t* offs = offsets_on_device(c, st);
+  const DenseArgs a = dense_args(c, kEye34);  // (the kernel puts each item's pose in)
   const RefinePlan plan = refine_plan((unsigned long long)n, every, poses);
   const unsigned long long items = (unsigned long long)poses * plan.tiles;  // (at most 2^22: refine_plan's chunk)
   {
-    const uint32_t blocks = (uint32_t)(items < (unsigned long long)kNearestBlocks ? items : (unsigned long long)kNearestBlocks);
+    const uint32_t blocks = capped_blocks(items);
     // DESIGN.md §Dense map, Refining: run_align's model per (pose, kept point) (the point, 16, and
     // the own cell's key word, 8; the other lookups, and the plane form's 16 B per found point,
     // are not known at launch), the item's pose (96) and its partial record (256)
@@ -2004,7 +2015,7 @@ void run_refine(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, uint3
     const auto launch = [&](auto rows) {
       hipLaunchKernelGGL(k_refine<decltype(rows)>, dim3(blocks), dim3(kDenseThreads), 0, st, d_pts, plan.kept, every,
                          Rf.poses.p, plan.tiles, (uint32_t)items, a, probe_take_args(c, f), reach, max_dist2, 1.0 / sigma,
-                         N.offs.p, D.keys.p, D.hits.p, D.xyz.p, Rf.part.p, rows);
+                         offs, D.keys.p, D.hits.p, D.xyz.p, Rf.part.p, rows);
     };
     if (plane) launch(PlaneRows{D.normals.nrm.p});
     else launch(PointRows{});
@@ -2023,18 +2034,11 @@ void run_refine(fmx_ctx* c, const float4* d_pts, size_t n, uint32_t every, uint3
 static DenseTake normals_take_args(const fmx_ctx* c, const fmx_normals_params& prm) {
   return probe_take_args(c, probe_filter(prm.min_hits, prm.miss_num, prm.miss_den));
 }
-static uint32_t scan_blocks(uint64_t slots) {
-  return (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (slots + kDenseThreads - 1) / kDenseThreads);
-}
 
 void run_normals_build(fmx_ctx* c, const fmx_normals_params& prm, hipStream_t st) {
   auto& D = c->dense;
-  auto& N = D.nearest;
   auto& M = D.normals;
-  if (!N.have) {  // the cube's offsets in shell order, once per context (shared with run_nearest)
-    FMX_HIP(hipMemcpyAsync(N.offs.p, N.h_offs.data(), N.h_offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    N.have = true;
-  }
+  const uint32_t* offs = offsets_on_device(c, st);
   const NormalsArgs na{prm.reach, normals_min_support(prm), prm.max_dist2, prm.max_flatness};
   FMX_HIP(hipMemsetAsync(M.cnt.p, 0, 8 * sizeof(unsigned long long), st));
   // DESIGN.md §Dense map, Normals: every slot's key word read (8); per voxel its hits and point
@@ -2043,7 +2047,7 @@ void run_normals_build(fmx_ctx* c, const fmx_normals_params& prm, hipStream_t st
   // own `lookups` gives the first)
   ProfScope ps(c->prof, PROF_DENSE, (double)D.slots * 8.0 + (double)D.voxels * 56.0, st);
   hipLaunchKernelGGL(k_normals_build, dim3(scan_blocks(D.slots)), dim3(kDenseThreads), 0, st, D.keys.p, D.hits.p, D.xyz.p,
-                     D.slots, normals_take_args(c, prm), na, N.offs.p, M.nrm.p, M.support.p, M.cnt.p);
+                     D.slots, normals_take_args(c, prm), na, offs, M.nrm.p, M.support.p, M.cnt.p);
   FMX_HIP(hipGetLastError());
 }
 
@@ -2121,7 +2125,7 @@ uint32_t run_dense_count(fmx_ctx* c, uint32_t min_hits, uint32_t miss_num, uint3
   const DenseTake tk = dense_take_args(c, min_hits, miss_num, miss_den, false);
   FMX_HIP(hipMemsetAsync(D.out_n.p, 0, sizeof(uint32_t), st));
   {
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (D.slots + kDenseThreads - 1) / kDenseThreads);
+    const uint32_t blocks = scan_blocks(D.slots);
     // every slot's hit count (+ its miss count under a miss filter; short-circuits not counted)
     ProfScope ps(c->prof, PROF_DENSE, (double)D.slots * (tk.misses ? 8.0 : 4.0), st);
     hipLaunchKernelGGL(k_dense_count, dim3(blocks), dim3(kDenseThreads), 0, st, D.hits.p, D.slots, tk, D.out_n.p);
@@ -2143,7 +2147,7 @@ void run_dense_compact(fmx_ctx* c, uint32_t min_hits, uint32_t miss_num, uint32_
   const DenseTake tk = dense_take_args(c, min_hits, miss_num, miss_den, with_misses);
   uint32_t* o_miss = with_misses && D.carve.have ? D.carve.o_miss.p : nullptr;
   FMX_HIP(hipMemsetAsync(D.out_n.p, 0, sizeof(uint32_t), st));
-  const uint32_t blocks = (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (D.slots + kDenseThreads - 1) / kDenseThreads);
+  const uint32_t blocks = scan_blocks(D.slots);
   // every slot's hit count, twice (2 * 4) + per voxel taken its tag and point read and
   // written, its hit count written (2 * (8 + 24) + 4); with the miss array in play each
   // slot's miss count twice more (2 * 4) and a taken voxel's written (4)
@@ -2184,7 +2188,7 @@ void run_roll_count(fmx_ctx* c, const long long cc[3], const uint32_t half[3], u
   D.h_n.ensure(2);
   FMX_HIP(hipMemsetAsync(D.roll.n.p, 0, 4 * sizeof(uint32_t), st));
   {
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (D.slots + kDenseThreads - 1) / kDenseThreads);
+    const uint32_t blocks = scan_blocks(D.slots);
     ProfScope ps(c->prof, PROF_DENSE, (double)D.slots * 8.0, st);  // every slot's key
     hipLaunchKernelGGL(k_roll_count, dim3(blocks), dim3(kDenseThreads), 0, st, D.keys.p, D.slots, roll_box(cc, half),
                        D.roll.n.p);
@@ -2207,7 +2211,7 @@ void run_roll_rebuild(fmx_ctx* c, const long long cc[3], const uint32_t half[3],
   auto& Cv = D.carve;
   const double mb = Cv.have ? 1.0 : 0.0;  // (the miss word wherever the hit word goes; seen zeroed)
   {
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kDenseScanBlocks, (D.slots + kDenseThreads - 1) / kDenseThreads);
+    const uint32_t blocks = scan_blocks(D.slots);
     // every slot's key, twice (2 * 8) + per evicted voxel its tag, hits and point read and
     // written, its slot emptied (2 * 36 + 20) + per kept voxel the same and its key written (+ 8)
     ProfScope ps(c->prof, PROF_DENSE,

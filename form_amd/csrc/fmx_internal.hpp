@@ -685,24 +685,19 @@ struct fmx_ctx {
       fmx::DBuf<uint32_t> ticket;
       fmx::HBuf<double> h_out;
     } align;
-    // scoring (fmx_score_poses; densemap.hip, the score block): a chunk's staged poses (12
-    // doubles each), its (pose, tile) partial records and its poses' records.  The offsets are
-    // `nearest`'s, the staged scan is `in`; nothing is shared with `align`.  Nothing here is
-    // allocated, and nothing launched, unless that entry point is called
-    struct Score {
+    // scoring (fmx_score_poses) and refining (fmx_refine_systems, fmx_refine_poses; densemap.hip,
+    // the score and refine blocks): a chunk's staged poses (12 doubles each), its (pose, tile)
+    // partial records and its poses' records.  The offsets are `nearest`'s, the staged scan is
+    // `in`; the two share nothing with `align` or with each other.  Nothing here is allocated,
+    // and nothing launched, unless one of a feature's entry points is called
+    template <class Part, class Out>
+    struct PoseBatch {
       fmx::DBuf<double> poses;
-      fmx::DBuf<fmx_pose_score> part, out;
-    } score;
-    // refining (fmx_refine_systems, fmx_refine_poses; densemap.hip, the refine block): a chunk's
-    // staged poses (12 doubles each), its (pose, tile) partial records and its poses' records.
-    // The offsets are `nearest`'s, the staged scan is `in`; nothing is shared with `align` or
-    // `score`.  Nothing here is allocated, and nothing launched, unless one of the two entry
-    // points is called
-    struct Refine {
-      fmx::DBuf<double> poses;
-      fmx::DBuf<fmx::RefinePart> part;
-      fmx::DBuf<fmx_refine_system> out;
-    } refine;
+      fmx::DBuf<Part> part;
+      fmx::DBuf<Out> out;
+    };
+    PoseBatch<fmx_pose_score, fmx_pose_score> score;
+    PoseBatch<fmx::RefinePart, fmx_refine_system> refine;
     // surface normals (fmx_normals_*, read by fmx_plane_*; densemap.hip, the normals block):
     // one snapshot per build, exactly `slots` entries each (+ 20 B per slot): {n0, n1, n2,
     // flatness} and the support.  `current` is the one host-side flag every call that changes

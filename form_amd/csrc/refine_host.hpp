@@ -1,7 +1,7 @@
 // refine_host.hpp — the host-only parts of refining many candidate poses of a scan against the
 // dense map (include/fmx/fmx.h, fmx_refine_systems, fmx_refine_poses and fmx_refine_plan;
 // densemap.hip, the refine block): the argument checks on top of score_check and align_check,
-// the plan (tiling and chunking, the one place their constants live) and the lockstep
+// the plan (align_host.hpp's batch_plan at the refine tile and record) and the lockstep
 // Gauss-Newton loop over a callable that evaluates the systems of a list of poses, so that the
 // loop runs without a device.  No device code and no HIP header: tests/cpp/test_refine_host.cpp
 // builds it alone, under the host sanitizers.
@@ -29,9 +29,6 @@ namespace fmx {
 #define FMX_REFINE_TILE 256
 #endif
 constexpr uint32_t kRefineTile = FMX_REFINE_TILE;
-constexpr uint32_t kRefineGridCap = 2048;      // blocks of the first launch at the most (k_nearest's cap)
-constexpr uint32_t kRefineChunkPoses = 16384;  // poses per chunk at the most
-constexpr uint64_t kRefinePartialBytes = 32ull << 20;  // ... and the partial records of a chunk
 static_assert(kRefineTile >= 256 && kRefineTile % 256 == 0, "a tile is a whole number of block-wide passes");
 
 // One (pose, tile) partial record, written whole by the item's block.
@@ -65,27 +62,16 @@ inline fmx_status refine_loop_check(double threshold, const char** why) {
   return align_loop_check(any, threshold, why);
 }
 
-// The tiling and chunking of a call (fmx_refine_plan's out, in its order).
-struct RefinePlan {
-  uint32_t kept, tile, tiles, chunk, chunks, cap;
-};
-// n < 2^32 (the caller checked): the kept points fit a word.
+// The plan of a call (align_host.hpp, batch_plan).
+using RefinePlan = BatchPlan;
 inline RefinePlan refine_plan(unsigned long long n, uint32_t stride, uint32_t n_poses) {
-  RefinePlan p{};
-  p.kept = (uint32_t)align_kept(n, stride ? stride : 1u);
-  p.tile = kRefineTile;
-  p.tiles = (uint32_t)(((unsigned long long)p.kept + kRefineTile - 1) / kRefineTile);
-  const uint64_t fit = kRefinePartialBytes / sizeof(RefinePart) / (p.tiles ? p.tiles : 1u);
-  p.chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kRefineChunkPoses, fit));
-  p.chunks = p.kept ? (n_poses + p.chunk - 1) / p.chunk : 0u;
-  p.cap = kRefineGridCap;
-  return p;
+  return batch_plan(n, stride, n_poses, kRefineTile, sizeof(RefinePart));
 }
 
 // align_loop_as's recurrence for n_poses poses in lockstep.  systems_at(poses, count, records)
 // evaluates the systems of `count` poses (12 doubles each) into `count` records; each round it
-// gets the poses still running, in list order.  Pose k steps with the very functions
-// align_loop_as uses, so that its pose and result are what the one-pose loop gives.  A singular
+// gets the poses still running, in list order.  Pose k steps with align_loop_as's gn_step, so
+// that its pose and result are what the one-pose loop gives.  A singular
 // system ends its pose: singular = 1, poses_out[k] = poses_init[k].  poses_out and results (may
 // be NULL) are written at the end; may throw std::bad_alloc before the first evaluation.
 template <class SystemsAt>
@@ -118,19 +104,12 @@ void refine_loop(const double* poses_init, uint32_t n_poses, uint32_t max_iters,
       r.error = s.S[28];
       r.found = s.found, r.none = s.none, r.out_of_range = s.out_of_range, r.invalid = s.invalid;
       r.unoriented = s.unoriented, r.lookups = s.lookups;
-      double H[6][6], g[6], dx[6];
-      align_unpack(s.S, H, g);
-      if (!fmxh::chol_solve6(H, g, dx)) {
+      if (!gn_step(s.S, T[k], threshold, &r.last_step, &r.converged)) {
         r.singular = 1;
         r.converged = 0;
         std::memcpy(T[k].m, poses_init + (size_t)k * 12, sizeof(T[k].m));
         continue;
       }
-      T[k] = fmxh::compose(T[k], fmxh::expmap(dx));
-      double n2 = 0.0;
-      for (double x : dx) n2 += x * x;
-      r.last_step = std::sqrt(n2);
-      r.converged = r.last_step < threshold ? 1 : 0;
       if (!r.converged && r.iters < max_iters) active[left++] = k;
     }
     active.resize(left);

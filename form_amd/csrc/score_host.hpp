@@ -1,7 +1,7 @@
 // score_host.hpp — the host-only parts of scoring many candidate poses of a scan against the
 // dense map (include/fmx/fmx.h, fmx_score_poses and fmx_score_plan; densemap.hip, the score
-// block): the argument checks on top of align_check, the plan (tiling and chunking, the one
-// place their constants live) and the ranking rule of the Python layer, restated.  No device
+// block): the argument checks on top of align_check, the plan (align_host.hpp's batch_plan at
+// the score tile) and the ranking rule of the Python layer, restated.  No device
 // code and no HIP header: tests/cpp/test_score_host.cpp builds it alone, under the host
 // sanitizers.
 #pragma once
@@ -16,10 +16,7 @@
 
 namespace fmx {
 
-constexpr uint32_t kScoreTile = 256;          // kept points per work item: one block-wide pass
-constexpr uint32_t kScoreGridCap = 2048;      // blocks of the first launch at the most (k_nearest's cap)
-constexpr uint32_t kScoreChunkPoses = 16384;  // poses per chunk at the most
-constexpr uint64_t kScorePartialBytes = 32ull << 20;  // ... and the partial records of a chunk
+constexpr uint32_t kScoreTile = 256;  // kept points per work item: one block-wide pass
 
 static_assert(sizeof(fmx_pose_score) == 32, "a score record is 32 bytes");
 
@@ -45,25 +42,13 @@ inline fmx_status score_check(const void* points, unsigned long long n, const do
       *why = "non-finite pose";
       return FMX_E_INVAL;
     }
-  const double eye[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};  // (the poses are checked above)
-  return align_check(points, n, eye, prm, why);
+  return align_check(points, n, kEye34, prm, why);  // (the poses are checked above)
 }
 
-// The tiling and chunking of a call (fmx_score_plan's out, in its order).
-struct ScorePlan {
-  uint32_t kept, tile, tiles, chunk, chunks, cap;
-};
-// n < 2^32 (the caller checked): the kept points fit a word.
+// The plan of a call (align_host.hpp, batch_plan): a partial record is a score record.
+using ScorePlan = BatchPlan;
 inline ScorePlan score_plan(unsigned long long n, uint32_t stride, uint32_t n_poses) {
-  ScorePlan p{};
-  p.kept = (uint32_t)align_kept(n, stride ? stride : 1u);
-  p.tile = kScoreTile;
-  p.tiles = (uint32_t)(((unsigned long long)p.kept + kScoreTile - 1) / kScoreTile);
-  const uint64_t fit = kScorePartialBytes / sizeof(fmx_pose_score) / (p.tiles ? p.tiles : 1u);
-  p.chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kScoreChunkPoses, fit));
-  p.chunks = p.kept ? (n_poses + p.chunk - 1) / p.chunk : 0u;
-  p.cap = kScoreGridCap;
-  return p;
+  return batch_plan(n, stride, n_poses, kScoreTile, sizeof(fmx_pose_score));
 }
 
 // before(a, b): record i = a ranks ahead of record j = b.  found descending, then sum_d2
